@@ -13,10 +13,13 @@ train on the first 100K vectors (k-means++ from mt19937(42), 10 Lloyd iterations
 exactly ivf_flat_index.cpp:49-145), then add all vectors. Data are synthetic
 iid N(0,1) draws generated on the device.
 
-Rank 0 at N=1 also times the CPU oracle (oracle/, the restatement of the
-reference's CPU search path) on a bounded sample of the same queries against the
-same index, single-threaded like the reference (ivf_flat_index.cpp:214), and
-checks the GPU results of that sample bit for bit.
+A plain run builds the index, warms up, times the K steps and prints the result line
+(QPS, ms_per_step, the K steps' own p99). --dump-outputs DIR also writes the last timed
+step's distances and ids to DIR. Everything else is behind --full: the 1000-batch latency
+legs, the one-at-a-time roofline pass, the footprint, and at N=1 rank 0 times the CPU
+oracle (oracle/, the restatement of the reference's CPU search path) on a bounded sample
+of the same queries against the same index, single-threaded like the reference
+(ivf_flat_index.cpp:214), and checks the GPU results of that sample bit for bit.
 """
 from __future__ import annotations
 
@@ -662,7 +665,21 @@ def main():
                     help="--emulate-rank all in this one process (round 3's form) instead of a process per rank")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="engine tuning knob (vdb_ivf_set_option), e.g. wide_stride=1; results never change")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the timed steps: the latency legs, the one-at-a-time roofline pass, the footprint, "
+                         "the CPU baseline with its parity checks, and the legs --host-api, --tier-cache-gib, "
+                         "--shard-check and --emulate-rank all ask for")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's results to DIR/distances.npy (float32) and DIR/ids.npy (float64)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run sets up, warms up, times the K steps and prints the line: nothing else
+        asked = [o for o, on in (("--host-api", args.host_api), ("--tier-cache-gib", args.tier_cache_gib > 0),
+                                 ("--shard-check", args.shard_check > 0),
+                                 ("--emulate-rank all", args.emulate_rank in ("all", "assign") or args.asg_file)) if on]
+        if asked:
+            ap.error(", ".join(asked) + ": needs --full")
+        args.latency_batches = args.prof_steps = 0
     if args.emulate_rank in ("all", "assign") or args.asg_file:
         args.sharded_build = True  # every rank's shard from one assignment pass
         args.emulate_shard = args.emulate_shard or 8
@@ -849,6 +866,10 @@ def timed_region(vdb, idx, args, device, rank, world, queries, out_d, out_i, che
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    last = None
+    if args.dump_outputs:  # what the last timed step returned, before any later leg reuses the rows
+        r0 = (args.warmup + args.steps - 1) * B
+        last = (out_d[r0:r0 + B].cpu().numpy(), out_i[r0:r0 + B].cpu().numpy())
     parity_multi = None
     if check is not None:
         q0, nchk, chk_d, chk_i = check
@@ -875,6 +896,9 @@ def timed_region(vdb, idx, args, device, rank, world, queries, out_d, out_i, che
         p99, lat_mean = lat_legs[len(streams)]["p99_ms"], lat_legs[len(streams)]["mean_ms"]
     else:
         p99, lat_mean = p99_steps, sum(lat) / max(len(lat), 1)
+    if not args.full:  # a plain run: the K timed steps only
+        return {"elapsed": elapsed, "p99": p99, "lat_mean": lat_mean, "p99_steps": p99_steps, "latency_legs": lat_legs,
+                "parity_multi": parity_multi, "last_step": last}
 
     device_wait(args, world, idx, streams, rank)
     idx.profile_enable(True)
@@ -927,7 +951,7 @@ def timed_region(vdb, idx, args, device, rank, world, queries, out_d, out_i, che
         p99_single = lat_legs[1]["p99_ms"]
     return {"elapsed": elapsed, "p99": p99, "lat_mean": lat_mean, "p99_single": p99_single, "prof": prof,
             "p99_steps": p99_steps, "latency_legs": lat_legs,
-            "parity_multi": parity_multi,
+            "parity_multi": parity_multi, "last_step": last,
             "per_rank": per_rank, "mine": mine}
 
 
@@ -1229,8 +1253,77 @@ def run(vdb, args, device, rank, world):
         idx.set_option("exchange_emulate_world", args.emulate_shard)
         idx.attach_comm(vdb.comm_unique_id(), 0, 1)
     res = timed_region(vdb, idx, args, device, rank, world, queries, out_d, out_i, check)
-    elapsed, p99, p99_single, prof = res["elapsed"], res["p99"], res["p99_single"], res["prof"]
+    elapsed, p99 = res["elapsed"], res["p99"]
     parity_multi = res["parity_multi"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *res["last_step"])
+
+    result = {
+        "metric": METRIC,
+        "value": round(args.steps * B / elapsed, 1),
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+        "p99_ms": round(p99, 4),
+        # (--full: p99 from >= 1000-batch latency legs; the K timed steps' own p99 beside it)
+        "p99_samples": args.latency_batches if res["latency_legs"] else args.steps,
+        "p99_ms_timed_steps": round(res["p99_steps"], 4),
+        "latency_legs": list(res["latency_legs"].values()),
+        # with `inflight` batches in flight a batch's latency is at least inflight x ms_per_step
+        # on average (Little's law); p99 / mean shows the spread around that
+        "latency_mean_ms": round(res["lat_mean"], 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": ("synthetic: iid N(0,1) fp32 vectors generated on device (seed 12345), queries seed 12346"
+                 if args.data == "iid" else
+                 f"synthetic: two-level Gaussian mixture, {args.centers.shape[0]} components in super-clusters of "
+                 f"{args.mix_group or args.nprobe} (supers N(0,1) seed 777, components +{args.mix_spread} N(0,1) seed 778, "
+                 f"points +{args.mix_sigma} N(0,1)) generated on device (seed 12345), queries from the same mixture "
+                 f"(seed 12346)"),
+        "config": {
+            "workload": f"{args.nvec // 1_000_000}M x {args.dim}D IVF-Flat L2, nlist {args.nlist}, nprobe {args.nprobe}, "
+                        f"batch {B}, k {k}",
+            "nvec": args.nvec, "dim": args.dim, "nlist": args.nlist, "nprobe": args.nprobe, "batch": B, "k": k,
+            "train_vectors": min(args.train, args.nvec),
+            "parallelism": (f"lists sharded over {world} rank(s) ({'probe-weighted ' if args.plan == 'weighted' else ''}LPT), one all-gather per batch of per-rank top-k "
+                            + (" (engine RCCL communicator, vdb_ivf_attach_comm)" if args.exchange == "engine" else
+                               f" (torch.distributed {'RCCL' if args.dist_backend == 'nccl' else 'gloo, host-staged'})")
+                            if world > 1 else "single GPU") + f"; {args.inflight} batches in flight",
+        },
+        "build": build_info,
+        "engine_options": dict(o.split("=", 1) for o in args.opt),
+        **({"rehearsal": f"{world} ranks on {torch.cuda.device_count()} GPU(s), host-staged exchange: "
+                         "protocol check, not a scaling number"} if args.rehearsal else {}),
+        **({"emulated_shard": f"rank {er} of {args.emulate_shard} (partial results; diagnostic, not a bench line)"}
+           if args.emulate_shard > 1 else {}),
+    }
+    if parity_multi is not None:
+        result["parity_vs_single_gpu"] = {"batches": min(args.check_batches, args.steps), "bit_identical": parity_multi}
+    if args.full:
+        full_legs(vdb, idx, args, device, rank, world, er, queries, out_d, out_i, res, result)
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+
+
+def dump_outputs(d, dist, ids):
+    """--dump-outputs: the last timed step's results as a caller receives them, one row per
+    query of the batch: distances.npy (float32, B x k) and ids.npy (B x k; the uint64 ids as
+    float64, exact below 2^53, the empty-slot id 2^64 - 1 as -1)."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "distances.npy"), np.ascontiguousarray(dist, dtype=np.float32))
+    np.save(os.path.join(d, "ids.npy"), ids.view(np.int64).astype(np.float64))
+
+
+def full_legs(vdb, idx, args, device, rank, world, er, queries, out_d, out_i, res, result):
+    """--full: what the line holds beyond the timed steps' figures — the roofline of the
+    dominant kernel (from timed_region's one-at-a-time pass), the footprint, and the legs
+    that run after the timed region (host API, CPU baseline and parity, shard parity, tier)."""
+    B, k = args.batch, args.k
+    p99_single, prof = res["p99_single"], res["prof"]
 
     launches = max(prof["scan_launches"], 1)
     scan_ms = prof["scan_ms"] / launches
@@ -1273,43 +1366,8 @@ def run(vdb, args, device, rank, world):
         key += "/" + ",".join(sorted(args.opt))
     traffic, traffic_note = lookup_traffic(args.traffic_json, key, vdb.build_id())
 
-    result = {
-        "metric": METRIC,
-        "value": round(args.steps * B / elapsed, 1),
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
-        "p99_ms": round(p99, 4),
+    result.update({
         "p99_ms_one_in_flight": round(p99_single, 4),
-        # (p99 from >= 1000-batch latency legs; the K timed steps' own p99 beside it)
-        "p99_samples": args.latency_batches if res["latency_legs"] else args.steps,
-        "p99_ms_timed_steps": round(res["p99_steps"], 4),
-        "latency_legs": list(res["latency_legs"].values()),
-        # with `inflight` batches in flight a batch's latency is at least inflight x ms_per_step
-        # on average (Little's law); p99 / mean shows the spread around that
-        "latency_mean_ms": round(res["lat_mean"], 4),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "fp32",
-        "data": ("synthetic: iid N(0,1) fp32 vectors generated on device (seed 12345), queries seed 12346"
-                 if args.data == "iid" else
-                 f"synthetic: two-level Gaussian mixture, {args.centers.shape[0]} components in super-clusters of "
-                 f"{args.mix_group or args.nprobe} (supers N(0,1) seed 777, components +{args.mix_spread} N(0,1) seed 778, "
-                 f"points +{args.mix_sigma} N(0,1)) generated on device (seed 12345), queries from the same mixture "
-                 f"(seed 12346)"),
-        "config": {
-            "workload": f"{args.nvec // 1_000_000}M x {args.dim}D IVF-Flat L2, nlist {args.nlist}, nprobe {args.nprobe}, "
-                        f"batch {B}, k {k}",
-            "nvec": args.nvec, "dim": args.dim, "nlist": args.nlist, "nprobe": args.nprobe, "batch": B, "k": k,
-            "train_vectors": min(args.train, args.nvec),
-            "parallelism": (f"lists sharded over {world} rank(s) ({'probe-weighted ' if args.plan == 'weighted' else ''}LPT), one all-gather per batch of per-rank top-k "
-                            + (" (engine RCCL communicator, vdb_ivf_attach_comm)" if args.exchange == "engine" else
-                               f" (torch.distributed {'RCCL' if args.dist_backend == 'nccl' else 'gloo, host-staged'})")
-                            if world > 1 else "single GPU") + f"; {args.inflight} batches in flight",
-        },
         "roofline": {
             "bound": "hbm",
             "kernel": "ivf_screen_collect" if deferred else ("ivf_scan_screen" if screened else "ivf_scan_wide"),
@@ -1346,19 +1404,11 @@ def run(vdb, args, device, rank, world):
                 "recheck_bytes_per_batch": int(prof["exact_reranks"] / batches * 4 * dp)} if deferred else {}),
         },
         "footprint": footprint(idx, args, world),
-        "build": build_info,
         **({"list_cache": idx.cache_stats()} if any(o.startswith("list_cache_bytes=") for o in args.opt) else {}),
-        "engine_options": dict(o.split("=", 1) for o in args.opt),
-        **({"rehearsal": f"{world} ranks on {torch.cuda.device_count()} GPU(s), host-staged exchange: "
-                         "protocol check, not a scaling number"} if args.rehearsal else {}),
-        **({"emulated_shard": f"rank {er} of {args.emulate_shard} (partial results; diagnostic, not a bench line)"}
-           if args.emulate_shard > 1 else {}),
-    }
+    })
     if res["per_rank"]:
         result["per_rank"] = res["per_rank"]
         result["rank_balance"] = balance(res["per_rank"])
-    if parity_multi is not None:
-        result["parity_vs_single_gpu"] = {"batches": min(args.check_batches, args.steps), "bit_identical": parity_multi}
     if args.host_api and world == 1:
         result["host_api"] = host_api_leg(idx, args, queries, out_d, out_i)
     if world == 1 and rank == 0 and not args.no_cpu and args.emulate_shard <= 1:
@@ -1372,9 +1422,6 @@ def run(vdb, args, device, rank, world):
         tq = torch.empty((args.tier_call * args.tier_calls, args.dim), dtype=torch.float32, device=device)
         fill_rows(vdb, args, tq, 1 << 40, tq.shape[0], 12346, torch.cuda.current_stream().cuda_stream)
         result["tier"] = tier_leg(vdb, idx, args, device, tq)
-        idx = None
-    if rank == 0:
-        print(json.dumps(result), flush=True)
 
 
 if __name__ == "__main__":

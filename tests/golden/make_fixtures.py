@@ -4,7 +4,8 @@ Each fixture holds the inputs the reference's own tests use (or a hand-built edg
 case) and the expected outputs of the reference CPU path restatement
 (oracle/cpu_ref.cpp): trained centroids, list sizes, and (ids, distance bits) of the
 search. Inputs that come from std::mt19937 + std::normal_distribution<float> are
-stored too, so a fixture is self-contained data.
+stored too, so a fixture is self-contained data; the one input set too large for a
+committed file is stored as its generator arguments and SHA-256 (trained_case).
 
 Run: python tests/golden/make_fixtures.py
 """
@@ -15,7 +16,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, os.path.dirname(HERE))
 import oracle  # noqa: E402
+from golden_data import input_digest  # noqa: E402
 
 
 def save(name, **arrays):
@@ -23,12 +26,18 @@ def save(name, **arrays):
     print("wrote", name, {k: v.shape for k, v in arrays.items()})
 
 
-def trained_case(name, X, Q, ids, dim, nlist, train_n, nprobe, k, metric=0):
+def trained_case(name, X, Q, ids, dim, nlist, train_n, nprobe, k, metric=0, generator=None):
+    """generator = (n, q, d, seed): the inputs are oracle.reference_test_data(*generator); the
+    fixture then stores these arguments and the inputs' SHA-256 instead of the inputs (for inputs
+    that would make the file larger than 1 MiB; tests/golden_data.py regenerates and checks them)."""
     o = oracle.OracleIndex(dim, nlist, metric)
     o.train(X[:train_n])
     o.add(X, ids)
     D, I = o.search(Q, nprobe, k)
-    save(name, X=X, Q=Q, ids=ids, params=np.array([dim, nlist, train_n, nprobe, k, metric], np.int64),
+    inputs = dict(X=X, Q=Q, ids=ids)
+    if generator is not None:
+        inputs = dict(generator=np.array(generator, np.int64), input_sha256=np.array(input_digest(X, Q, ids)))
+    save(name, **inputs, params=np.array([dim, nlist, train_n, nprobe, k, metric], np.int64),
          centroids=o.centroids, list_sizes=np.array([o.list_count(l) for l in range(nlist)], np.uint64),
          D=D, I=I)
 
@@ -40,7 +49,7 @@ def main():
                  np.arange(1000, dtype=np.uint64), 64, 16, 100, 4, 5)
     # test/CMakeLists.txt:56 — gpu_vs_cpu_test 10000 100 64 32 (nprobe 8, k 10, train 10000).
     X, Q, ids = oracle.reference_test_data(10000, 100, 64)
-    trained_case("gpu_vs_cpu_ctest", X, Q, ids, 64, 32, 10000, 8, 10)
+    trained_case("gpu_vs_cpu_ctest", X, Q, ids, 64, 32, 10000, 8, 10, generator=(10000, 100, 64, 12345))
     # bench/CMakeLists.txt:48 — benchmark 1000 64 32 5 (k 10); the re-seeded generator makes
     # query i == vector i (benchmark.cpp:130-138), 64 of its 10000 queries kept.
     X = oracle.gen_normal(42, 1000 * 64).reshape(1000, 64)

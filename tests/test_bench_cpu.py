@@ -41,3 +41,24 @@ def test_rank_balance_summary():
     assert b["scan_ms"]["argmax_rank"] == 3 and abs(b["scan_ms"]["max_over_min"] - 1.3) < 1e-9
     assert b["ms_per_step"]["argmax_rank"] == 0
     assert b["search_ms"]["max_over_min"] == 1.0
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import numpy as np
+    bench = _bench()
+    d = np.arange(6, dtype=np.float32).reshape(2, 3)
+    i = np.array([[5, 9_999_999, -1], [0, 1, 2]], np.int64)  # -1: the empty-slot id 2^64 - 1
+    bench.dump_outputs(str(tmp_path / "out"), d, i)
+    dd, ii = np.load(tmp_path / "out" / "distances.npy"), np.load(tmp_path / "out" / "ids.npy")
+    assert dd.dtype == np.float32 and np.array_equal(dd, d)
+    assert ii.dtype == np.float64 and np.array_equal(ii, i.astype(np.float64))
+
+
+def test_extra_legs_need_full(monkeypatch):
+    import pytest
+    import sys
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--host-api"])
+    with pytest.raises(SystemExit) as e:  # argparse error, before anything touches the GPU
+        bench.main()
+    assert e.value.code == 2

@@ -1,5 +1,5 @@
 """GPU parity at the BASELINE.json configurations' own sizes (configs[0] and configs[1]);
-configs[2] (10M x 768, the bench) is checked inside bench.py on a query sample
+configs[2] (10M x 768, the bench) is checked inside bench.py --full on a query sample
 (`cpu_baseline.parity_with_gpu`), and the 8-GPU configs through the sharding tests.
 
 * cfg1 — 100K x 128, gpu_vs_cpu_test.cpp's generator (mt19937(12345), database then queries):

@@ -369,7 +369,8 @@ GOLDEN_DIR = __import__("os").path.join(__import__("os").path.dirname(__file__),
                                   "empty_lists_dups"])
 def test_golden_fixture_on_gpu(name):
     import os
-    f = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+    from golden_data import load_golden
+    f = load_golden(os.path.join(GOLDEN_DIR, name + ".npz"))
     dim, nlist, train_n, nprobe, k, metric = (int(x) for x in f["params"])
     g = vdb.IVFFlatIndex(vdb.IVFFlatIndex.Config(dim, nlist, vdb.Metric(metric)))
     if train_n:

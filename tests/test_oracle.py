@@ -15,6 +15,7 @@ import pytest
 
 import oracle
 import oracle.np_ref as npr
+from golden_data import load_golden
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 U64MAX = np.iinfo(np.uint64).max
@@ -202,7 +203,7 @@ def test_count_only_lists_keep_shard_results():
 
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))), ids=os.path.basename)
 def test_golden_fixture(path):
-    f = np.load(path)
+    f = load_golden(path)
     dim, nlist, train_n, nprobe, k, metric = (int(x) for x in f["params"])
     o = oracle.OracleIndex(dim, nlist, metric)
     if train_n:

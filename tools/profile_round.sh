@@ -30,11 +30,11 @@ run() {  # run <name> <seconds> <cmd...>
     echo "[$(date +%T)] $name rc=$rc"
     if [ $rc -ne 0 ]; then tail -30 "$O/$name.log"; exit $rc; fi
 }
-SHORT="--steps 5 --warmup 1 --no-cpu --prof-steps 2 --latency-batches 0"
+SHORT="--full --steps 5 --warmup 1 --no-cpu --prof-steps 2 --latency-batches 0"
 # the bench lines read this call's PMC traffic, or the committed file when no traffic step ran
 TJ="$O/traffic.json"
 [[ ",$STEPS," == *",traffic"* ]] || TJ="$R/profiles/traffic.json"
-CFG4="--cfg cfg4 --emulate-shard 8 --no-cpu --inflight 3"
+CFG4="--full --cfg cfg4 --emulate-shard 8 --no-cpu --inflight 3"
 if has traffic; then
     run pmc_iid 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "ivf_scan_|ivf_screen_collect" -d "$O/pmc_iid" -o f -f csv -- python3 bench.py $SHORT
     run pmc_mix 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "ivf_scan_|ivf_screen_collect" -d "$O/pmc_mix" -o f -f csv -- python3 bench.py $SHORT --data mixture
@@ -58,18 +58,18 @@ if has mfma; then
     python3 tools/mfma_report.py "$O/pmc_mfma" "$O/trace_mfma" "$O/mfma.json" | tail -30
 fi
 if has bench; then
-    run bench 400 python3 -u bench.py --traffic-json "$TJ" --host-api
+    run bench 400 python3 -u bench.py --full --traffic-json "$TJ" --host-api
     grep '^{' "$O/bench.log" > "$O/bench.json" && cut -c 1-400 "$O/bench.json"
-    run bench_mix 400 python3 -u bench.py --traffic-json "$TJ" --data mixture --host-api
+    run bench_mix 400 python3 -u bench.py --full --traffic-json "$TJ" --data mixture --host-api
     grep '^{' "$O/bench_mix.log" > "$O/bench_mix.json" && cut -c 1-400 "$O/bench_mix.json"
 fi
 if has trace; then
     for inf in 1 3; do
-        run trace_inflight$inf 300 rocprofv3 --kernel-trace --stats -d "$O/trace_inflight$inf" -o k -f csv -- python3 bench.py --steps 20 --warmup 2 --no-cpu --inflight $inf --latency-batches 0
+        run trace_inflight$inf 300 rocprofv3 --kernel-trace --stats -d "$O/trace_inflight$inf" -o k -f csv -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu --inflight $inf --latency-batches 0
         find "$O/trace_inflight$inf" -name '*kernel_stats.csv' -exec cp {} "$O/kernel_stats_inflight$inf.csv" \;
         head -6 "$O/kernel_stats_inflight$inf.csv"
     done
-    run trace_mix 300 rocprofv3 --kernel-trace --stats -d "$O/trace_mix" -o k -f csv -- python3 bench.py --steps 20 --warmup 2 --no-cpu --inflight 1 --data mixture --latency-batches 0
+    run trace_mix 300 rocprofv3 --kernel-trace --stats -d "$O/trace_mix" -o k -f csv -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu --inflight 1 --data mixture --latency-batches 0
     find "$O/trace_mix" -name '*kernel_stats.csv' -exec cp {} "$O/kernel_stats_mixture.csv" \;
     head -6 "$O/kernel_stats_mixture.csv"
 fi
@@ -79,11 +79,11 @@ if has shard; then
 fi
 if has emu8; then
     # rank 0 of 8 cut from the headline index (the per-GPU work of the 8-GPU headline), 3 in flight
-    run emu8 600 python3 -u bench.py --emulate-shard 8 --inflight 3 --no-cpu --traffic-json "$TJ"
+    run emu8 600 python3 -u bench.py --full --emulate-shard 8 --inflight 3 --no-cpu --traffic-json "$TJ"
     grep '^{' "$O/emu8.log" > "$O/emu8.json" && cut -c 1-300 "$O/emu8.json"
 fi
 if has emu8trace; then
-    run trace_emu8 600 rocprofv3 --kernel-trace --stats -d "$O/trace_emu8" -o k -f csv -- python3 bench.py --emulate-shard 8 --steps 40 --warmup 4 --no-cpu --inflight 1 --prof-steps 4 --latency-batches 0
+    run trace_emu8 600 rocprofv3 --kernel-trace --stats -d "$O/trace_emu8" -o k -f csv -- python3 bench.py --full --emulate-shard 8 --steps 40 --warmup 4 --no-cpu --inflight 1 --prof-steps 4 --latency-batches 0
     find "$O/trace_emu8" -name '*kernel_stats.csv' -exec cp {} "$O/kernel_stats_emu8.csv" \;
     head -14 "$O/kernel_stats_emu8.csv" | cut -c 1-160
 fi

@@ -3,7 +3,7 @@
 # measurement of round 6 (profiles/INDEX.md names the tag and steps behind each record):
 #   bash tools/session.sh <tag> <step,step,...>
 #   smoke     __graft_entry__.smoke()
-#   multi     the two-rank rehearsal of the N-rank path on one GPU (bench.py --gpus 2)
+#   multi     the two-rank rehearsal of the N-rank path on one GPU (bench.py --full --gpus 2)
 #   grpc      the gRPC front end under load (tools/grpc_load.py)
 #   sweep     tools/knob_sweep.py $SWEEP_WL (default "s8 cfg3") over $SWEEP_SETS (engine option sets)
 #   trace8    the 1/8 shard at 3 in flight under a kernel trace, its timeline (tools/timeline.py)
@@ -42,7 +42,7 @@ if has smoke; then
     tail -2 "$O/smoke.log"
 fi
 if has multi; then
-    run multi 600 python -u bench.py --gpus 2 --steps 20 --warmup 3 --no-cpu --prof-steps 4
+    run multi 600 python -u bench.py --full --gpus 2 --steps 20 --warmup 3 --no-cpu --prof-steps 4
     grep '^{' "$O/multi.log" > "$O/multi.json"
     cut -c 1-400 "$O/multi.json"
 fi
@@ -52,18 +52,18 @@ if has grpc; then
     cat "$O/grpc.json"
 fi
 if has prof8; then
-    run prof8 400 rocprofv3 --kernel-trace --stats -d "$O/prof8" -o k -f csv -- python3 bench.py --emulate-shard 8 --inflight 1 --steps 30 --warmup 3 --no-cpu --latency-batches 0 --prof-steps 5
+    run prof8 400 rocprofv3 --kernel-trace --stats -d "$O/prof8" -o k -f csv -- python3 bench.py --full --emulate-shard 8 --inflight 1 --steps 30 --warmup 3 --no-cpu --latency-batches 0 --prof-steps 5
     find "$O/prof8" -name '*kernel_stats.csv' -exec cp {} "$O/kernel_stats_emu8.csv" \;
     cut -d, -f1-4 "$O/kernel_stats_emu8.csv" | cut -c1-150 | head -24
 fi
 if has trace8; then
     # the 1/8 shard at 3 in flight under a kernel trace: the timed region's timeline (tools/timeline.py)
-    run trace8 400 rocprofv3 --kernel-trace -d "$O/trace8" -o k -f csv -- python3 bench.py --emulate-shard 8 --inflight 3 --steps 100 --warmup 5 --no-cpu --latency-batches 0 --prof-steps 2
+    run trace8 400 rocprofv3 --kernel-trace -d "$O/trace8" -o k -f csv -- python3 bench.py --full --emulate-shard 8 --inflight 3 --steps 100 --warmup 5 --no-cpu --latency-batches 0 --prof-steps 2
     python3 tools/timeline.py "$(find "$O/trace8" -name '*kernel_trace.csv' | head -1)" 100 > "$O/timeline8.json" && cut -c1-1500 "$O/timeline8.json"
 fi
 if has prof3; then
     for inf in 1 2; do
-        run prof3_$inf 400 rocprofv3 --kernel-trace --stats -d "$O/prof3_$inf" -o k -f csv -- python3 bench.py --inflight $inf --steps 30 --warmup 3 --no-cpu --latency-batches 0 --prof-steps 5
+        run prof3_$inf 400 rocprofv3 --kernel-trace --stats -d "$O/prof3_$inf" -o k -f csv -- python3 bench.py --full --inflight $inf --steps 30 --warmup 3 --no-cpu --latency-batches 0 --prof-steps 5
         find "$O/prof3_$inf" -name '*kernel_stats.csv' -exec cp {} "$O/kernel_stats_inflight$inf.csv" \;
         cut -d, -f1-4 "$O/kernel_stats_inflight$inf.csv" | cut -c1-150 | head -16
     done
@@ -75,7 +75,7 @@ if has probe; then
 fi
 if has tier; then
     c=${TIER_GIB:-11.5}
-    run tier 1150 python3 -u bench.py --cfg cfg4 --emulate-shard 5 --steps 20 --warmup 2 --no-cpu --latency-batches 0 --prof-steps 3 \
+    run tier 1150 python3 -u bench.py --full --cfg cfg4 --emulate-shard 5 --steps 20 --warmup 2 --no-cpu --latency-batches 0 --prof-steps 3 \
         --tier-cache-gib $c --tier-call 512 --tier-calls 4 --tier-variant screen_recheck2=0 --tier-adapt 4096
     grep '^{' "$O/tier.log" > "$O/tier.json"
     python3 -c "
@@ -85,19 +85,19 @@ for v in t.get('variants', []): print('   ', v)
 print('resident', d['value'], d['ms_per_step'])"
 fi
 if has ranks3; then
-    run ranks3 900 python -u bench.py --cfg cfg3 --emulate-rank all --emulate-shard 8 --inflight 3 --no-cpu
+    run ranks3 900 python -u bench.py --full --cfg cfg3 --emulate-rank all --emulate-shard 8 --inflight 3 --no-cpu
     grep '^{' "$O/ranks3.log" > "$O/ranks3.json"
     cut -c 1-600 "$O/ranks3.json"
 fi
 if has ranks3q; then
     # the same with 4 workspace slots (a _variants/slots4 build), 4 batches in flight and 8 hardware
     # queues per process (4 in-flight streams + the communicator's each on a queue of their own)
-    run ranks3q 900 env VDB_IVF_LIB=$R/_variants/slots4/libvdb_ivf.so GPU_MAX_HW_QUEUES=8 python -u bench.py --cfg cfg3 --emulate-rank all --emulate-shard 8 --inflight 4 --no-cpu
+    run ranks3q 900 env VDB_IVF_LIB=$R/_variants/slots4/libvdb_ivf.so GPU_MAX_HW_QUEUES=8 python -u bench.py --full --cfg cfg3 --emulate-rank all --emulate-shard 8 --inflight 4 --no-cpu
     grep '^{' "$O/ranks3q.log" > "$O/ranks3q.json"
     cut -c 1-600 "$O/ranks3q.json"
 fi
 if has ranks4; then
-    run ranks4 1100 python -u bench.py --cfg cfg4 --emulate-rank all --emulate-shard 8 --inflight 3 --no-cpu
+    run ranks4 1100 python -u bench.py --full --cfg cfg4 --emulate-rank all --emulate-shard 8 --inflight 3 --no-cpu
     grep '^{' "$O/ranks4.log" > "$O/ranks4.json"
     cut -c 1-600 "$O/ranks4.json"
 fi
@@ -123,12 +123,12 @@ if has sweepv; then
     done
 fi
 if has ranks3v; then
-    run ranks3v 900 env VDB_IVF_LIB=$R/_variants/$VARIANT/libvdb_ivf.so python -u bench.py --cfg cfg3 --emulate-rank all --emulate-shard 8 --inflight 3 --no-cpu
+    run ranks3v 900 env VDB_IVF_LIB=$R/_variants/$VARIANT/libvdb_ivf.so python -u bench.py --full --cfg cfg3 --emulate-rank all --emulate-shard 8 --inflight 3 --no-cpu
     grep '^{' "$O/ranks3v.log" > "$O/ranks3v.json"
     cut -c 1-600 "$O/ranks3v.json"
 fi
 if has bench; then
-    run bench 600 python -u bench.py ${BENCH_ARGS}
+    run bench 600 python -u bench.py --full ${BENCH_ARGS}
     grep '^{' "$O/bench.log" > "$O/bench.json"
     cut -c 1-400 "$O/bench.json"
 fi
