@@ -41,6 +41,7 @@
 #include "../../include/vdb_ivf.h"
 #include "kernels.hpp"
 #include "floor.hpp"
+#include "row_reader.hpp"
 #include "uring.hpp"
 
 namespace vdbe {
@@ -359,8 +360,9 @@ struct vdb_ivf {
     // norms and ids of EVERY stored list stay HBM-resident (half the fp32 list bytes), packed
     // by sblock_off; the fp32 rows stay at the home and only the survivors' rows are read per
     // batch: straight from the page-locked host arena over PCIe, or, from a file home, by
-    // io_uring into page-locked staging and one copy to HBM (fetch_survivor_rows). No list is
-    // loaded into the cache for such a batch (the cache serves the exact-path searches).
+    // io_uring into page-locked staging and one copy to HBM (fetch_rows; the read loop itself
+    // is host-only code of its own, row_reader.hpp). No list is loaded into the cache for such
+    // a batch (the cache serves the exact-path searches).
     std::vector<uint64_t> sblock_off;  // tier: per stored list its first shadow block
     std::vector<uint32_t> sblist_host; // tier, file home: per shadow block its list
     uint64_t sblocks = 0;
@@ -370,7 +372,7 @@ struct vdb_ivf {
     DevBuf<char> fetch_bounce;         // ... O_DIRECT reads: 4 KiB-aligned supersets, one slot per read in flight
     bool tier_row_direct = true;       // option tier_row_direct: survivor rows with O_DIRECT (no page cache)
     uint32_t tier_row_qd = 256;        // option tier_row_qd: survivor-row reads in flight (their own ring)
-    std::unique_ptr<UringReader> row_uring;
+    RowReader row_reader;              // ... the reads themselves (its own ring)
     DevBuf<float> fetch_dev;           // ... on the device ([n][dim], padded into the slot's srows)
     std::vector<uint2> fetch_surv;     // ... their (slot, pair)
     uint64_t screen_rows_fetched = 0, screen_row_bytes = 0, screen_tier_batches = 0, screen_reruns = 0;
@@ -1175,134 +1177,93 @@ struct vdb_ivf {
         HIPCHECK(hipStreamSynchronize(stream));
     }
 
-    // Tier, file home: after the deferred scan's selection, read the survivors' rows of the
-    // batch from the file (one read each, io_uring on the buffered descriptor: hot rows stay in
-    // the page cache) into page-locked staging, copy them to the device and pad them to dp.
-    // Returns the rows ([survivor][dp]) for the exact pass, or nullptr when the candidate
-    // buffer overflowed (the caller re-runs the batch with a larger one).
-    const float* fetch_survivor_rows(SearchSlot& w, uint32_t cap, uint32_t& need, hipStream_t s) {
+    // Tier, file home: the survivors' rows of a screened batch, read from the file (or copied
+    // from the HBM cache) for the exact re-check. Three steps shared by the one-pass and the
+    // two-pass re-check, which differ only in how they lay the rows out:
+    //
+    // fetch_head: the batch's counters after the deferred scan's selection. False (need: the
+    // reserved candidate slots) when the candidate buffer overflowed: the caller re-runs the
+    // batch with a larger one. Else the survivors' download is queued on s (fetch_surv).
+    bool fetch_head(SearchSlot& w, uint32_t& n, uint32_t& need, hipStream_t s) {
         uint32_t hc[vdbk::kCounters];
         HIPCHECK(hipMemcpyAsync(hc, w.counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
         HIPCHECK(hipStreamSynchronize(s));
-        if (hc[vdbk::kCtrOvf]) {  // (some candidate fell beyond the buffer; need: the slots reserved)
+        if (hc[vdbk::kCtrOvf]) {  // (some candidate fell beyond the buffer)
             need = hc[vdbk::kCtrCand];
-            return nullptr;
+            return false;
         }
-        const uint32_t n = hc[vdbk::kCtrSurv];
+        n = hc[vdbk::kCtrSurv];
         fetch_surv.resize(n);
         if (n) HIPCHECK(hipMemcpyAsync(fetch_surv.data(), w.surv.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-        HIPCHECK(hipStreamSynchronize(s));
-        fetch_stage.host = true;
-        float* st = fetch_stage.ensure((size_t)std::max<uint32_t>(n, 1) * dim);
-        if (row_uring && row_uring->capacity() < tier_row_qd) row_uring.reset();
-        if (!row_uring) row_uring.reset(new UringReader(tier_row_qd));
-        UringReader* const ur = row_uring.get();
+        return true;
+    }
+
+    // fetch_rows: bring the rows of `want` ({shadow slot, staging row}; `nrows` staging rows)
+    // to the slot's device rows row0 .. row0 + nrows, padded to dp (`nsurv`: the batch's
+    // survivors, the capacity of the device buffers). A row whose list is in the HBM cache is
+    // copied from there (after the upload: it overwrites that row's unused staging content);
+    // the others are read from the file in slot order, O_DIRECT (where the file system allows
+    // it and option tier_row_direct asks for it) or buffered, so that hot rows stay in the
+    // page cache; a slot wanted for several staging rows is read once and copied to the
+    // others. Returns the device rows, the stream synchronized (the staging and the cache's
+    // contents are reused later).
+    std::vector<std::pair<uint64_t, uint32_t>> fetch_want;
+    float* fetch_rows(SearchSlot& w, uint32_t row0, uint32_t nrows, uint32_t nsurv, hipStream_t s) {
         const uint64_t row_bytes = (uint64_t)dim * 4;
-        // O_DIRECT (where the file system allows it): each read is the 4 KiB-aligned superset
-        // of the row into a bounce slot, copied out on completion; else a buffered read
-        // straight into the staging
+        cache_src_host.clear();
+        std::vector<std::pair<uint64_t, uint32_t>> file;
+        file.reserve(fetch_want.size());
+        for (const auto& sr : fetch_want) {
+            const uint32_t l = sblist_host[sr.first >> 6];
+            if (tier_row_cache && !cache_off.empty() && cache_off[l] != kAbsent)
+                cache_src_host.push_back({(unsigned long long)(row0 + sr.second),
+                                          (unsigned long long)(cache_off[l] * 64 + (sr.first - sblock_off[l] * 64))});
+            else
+                file.push_back(sr);
+        }
+        std::sort(file.begin(), file.end());
+        std::vector<RowReader::Req> reqs;
+        std::vector<std::pair<uint32_t, uint32_t>> dups;  // (staging row, the row its slot was read to)
+        reqs.reserve(file.size());
+        for (size_t t = 0; t < file.size(); ++t) {
+            if (t && file[t].first == file[t - 1].first) {
+                dups.push_back({file[t].second, reqs.back().row});
+                continue;
+            }
+            const uint32_t l = sblist_host[file[t].first >> 6];
+            reqs.push_back({file_off[l] + count[l] * 8 + (file[t].first - sblock_off[l] * 64) * row_bytes, file[t].second});
+        }
+        fetch_stage.host = true;
+        float* st = fetch_stage.ensure((size_t)std::max<uint32_t>(nrows, 1) * dim);
         const bool direct = tier_row_direct && home_fd_direct >= 0;
-        const uint32_t kQD = std::min(tier_row_qd, row_uring->capacity());
-        const uint64_t span = ((row_bytes + 4095) / 4096 + 1) * 4096;
         char* bounce = nullptr;
         if (direct) {
             fetch_bounce.host = true;
-            bounce = fetch_bounce.ensure(kQD * span + 4096);
-            bounce = (char*)(((uintptr_t)bounce + 4095) & ~(uintptr_t)4095);
+            bounce = fetch_bounce.ensure(row_reader.bounce_bytes(tier_row_qd, row_bytes));
         }
-        std::vector<uint32_t> slot_of(kQD), free_slots(kQD);
-        for (uint32_t i = 0; i < kQD; ++i) free_slots[i] = kQD - 1 - i;
-        std::vector<uint64_t> delta(kQD);
-        uint64_t bytes_read = 0;
-        // rows of lists in the HBM cache are copied from there (after the upload below); the
-        // rest: one read per distinct row (a row surviving for several queries is read once),
-        // issued in file order, the duplicates copied from the first reader's staging row
-        cache_src_host.clear();
-        std::vector<uint32_t> order;
-        order.reserve(n);
-        if (surv_hist.size() != nlist) surv_hist.assign(nlist, 0);
-        for (uint32_t i = 0; i < n; ++i) {
-            const uint64_t slot = fetch_surv[i].x;
-            const uint32_t l = sblist_host[slot >> 6];
-            ++surv_hist[l];
-            if (tier_row_cache && !cache_off.empty() && cache_off[l] != kAbsent)
-                cache_src_host.push_back({(unsigned long long)i,
-                                          (unsigned long long)(cache_off[l] * 64 + (slot - sblock_off[l] * 64))});
-            else
-                order.push_back(i);
-        }
-        const uint32_t nf = (uint32_t)order.size();
-        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-            return fetch_surv[x].x != fetch_surv[y].x ? fetch_surv[x].x < fetch_surv[y].x : x < y;
-        });
-        std::vector<uint32_t> uniq;
-        std::vector<std::pair<uint32_t, uint32_t>> dups;  // (survivor, survivor holding its row)
-        uniq.reserve(nf);
-        for (uint32_t t = 0; t < nf; ++t) {
-            if (t && fetch_surv[order[t]].x == fetch_surv[order[t - 1]].x) dups.push_back({order[t], uniq.back()});
-            else uniq.push_back(order[t]);
-        }
-        const uint32_t nu = (uint32_t)uniq.size();
-        uint32_t next = 0, done = 0;
         try {
-            while (done < nu) {
-                while (next < nu && next - done < kQD) {  // (<= kQD queued or in flight)
-                    const uint32_t si = uniq[next];
-                    const uint64_t slot = fetch_surv[si].x;
-                    const uint32_t l = sblist_host[slot >> 6];
-                    const uint64_t r = slot - sblock_off[l] * 64;
-                    const uint64_t off = file_off[l] + count[l] * 8 + r * row_bytes;
-                    if (direct) {
-                        const uint32_t b = free_slots.back();
-                        free_slots.pop_back();
-                        const uint64_t g = dio_align;  // (the file system's O_DIRECT granule)
-                        const uint64_t a0 = off / g * g, a1 = (off + row_bytes + g - 1) / g * g;
-                        delta[b] = off - a0;
-                        slot_of[b] = si;
-                        ur->read(home_fd_direct, bounce + (size_t)b * span, (uint32_t)(a1 - a0), a0,
-                                 ((uint64_t)b << 32) | si);
-                        bytes_read += a1 - a0;
-                    } else {
-                        ur->read(home_fd, st + (size_t)si * dim, (uint32_t)row_bytes, off, si);
-                        bytes_read += row_bytes;
-                    }
-                    ++next;
-                }
-                for (const UringReader::Done& d : ur->wait(1)) {
-                    const uint32_t b = (uint32_t)(d.tag >> 32), i = (uint32_t)d.tag;
-                    const int64_t want = direct ? (int64_t)(delta[b] + row_bytes) : (int64_t)row_bytes;
-                    require(d.result >= want,
-                            "short read of a survivor row from the list file" +
-                                (d.result < 0 ? std::string(": ") + std::strerror((int)-d.result) : ""),
-                            VDB_ERR_STATE);
-                    if (direct) {
-                        std::memcpy(st + (size_t)i * dim, bounce + (size_t)b * span + delta[b], row_bytes);
-                        free_slots.push_back(b);
-                    }
-                    ++done;
-                }
-            }
-        } catch (...) {
-            ur->drain();
-            throw;
+            // (with O_DIRECT: the aligned supersets the device delivered)
+            file_bytes_read += row_reader.read_rows(home_fd, direct ? home_fd_direct : -1, dio_align, tier_row_qd, row_bytes,
+                                                    reqs, (char*)st, bounce);
+        } catch (const RowReader::ShortRead& e) {
+            throw VdbError(VDB_ERR_STATE, e.what());
         }
         for (const auto& d : dups) std::memcpy(st + (size_t)d.first * dim, st + (size_t)d.second * dim, row_bytes);
-        screen_rows_fetched += nu;
-        screen_row_bytes += (uint64_t)nu * row_bytes;
+        screen_rows_fetched += reqs.size();
+        screen_row_bytes += reqs.size() * row_bytes;
         screen_rows_cached += cache_src_host.size();
-        file_bytes_read += bytes_read;  // (with O_DIRECT: the aligned supersets the device delivered)
-        float* rows = slot_buf(w, w.srows, (size_t)std::max<uint32_t>(n, 1) * dp);
-        if (n) {
+        float* rows = slot_buf(w, w.srows, (size_t)std::max<uint32_t>(nsurv, 1) * dp);
+        if (nrows) {
             if (dim == dp) {
-                HIPCHECK(hipMemcpyAsync(rows, st, (size_t)n * row_bytes, hipMemcpyHostToDevice, s));
+                HIPCHECK(hipMemcpyAsync(rows + (size_t)row0 * dp, st, (size_t)nrows * row_bytes, hipMemcpyHostToDevice, s));
             } else {
-                HIPCHECK(hipMemcpyAsync(fetch_dev.ensure((size_t)n * dim), st, (size_t)n * row_bytes,
-                                        hipMemcpyHostToDevice, s));
-                vdbk::launch_pad_rows(fetch_dev.p, n, dim, dp, rows, s);
+                HIPCHECK(hipMemcpyAsync(fetch_dev.ensure((size_t)std::max<uint32_t>(nsurv, 1) * dim), st,
+                                        (size_t)nrows * row_bytes, hipMemcpyHostToDevice, s));
+                vdbk::launch_pad_rows(fetch_dev.p, nrows, dim, dp, rows + (size_t)row0 * dp, s);
                 HIPCHECK(hipGetLastError());
             }
         }
-        if (!cache_src_host.empty()) {  // (overwrites those rows' unused staging content)
+        if (!cache_src_host.empty()) {
             // (a k > 64 call may have loaded lists into the cache asynchronously: its loads end
             // before its last sub-batch, whose completion tier_call_ev marks)
             if (tier_call_used) HIPCHECK(hipEventSynchronize(tier_call_ev));
@@ -1312,34 +1273,41 @@ struct vdb_ivf {
             vdbk::launch_gather_cache_rows(cache.p, d4, cache_src.p, nc, rows, s);
             HIPCHECK(hipGetLastError());
         }
-        HIPCHECK(hipStreamSynchronize(s));  // (the staging and the cache's contents are reused later)
+        HIPCHECK(hipStreamSynchronize(s));
         return rows;
     }
 
-    // Tier, file home, TWO-PASS re-check (option screen_recheck2): read the rows of the batch's
-    // survivors marked `phase` (1: pass A, each pair's k smallest lower bounds; 2: pass B, the
-    // others not above pass A's k-th exact distance; launch_tier_recheck) into the slot's
-    // compact device rows, after those of the earlier phase; a row needed again (the same
-    // vector surviving for another query, or in both phases) is read once. Rows of lists in the
-    // HBM cache are copied from there. The survivor -> row map is uploaded. Phase 1 returns
-    // false (need: the reserved candidate slots) when the candidate buffer overflowed: the
-    // caller re-runs the batch with a larger one.
+    // ONE-PASS re-check: one staging row per survivor, indexed by survivor (a row surviving for
+    // several queries is read once and copied; from the cache it is gathered once per survivor).
+    // Returns the rows ([survivor][dp]) for the exact pass, or nullptr when the candidate
+    // buffer overflowed (the caller re-runs the batch with a larger one).
+    const float* fetch_survivor_rows(SearchSlot& w, uint32_t& need, hipStream_t s) {
+        uint32_t n = 0;
+        if (!fetch_head(w, n, need, s)) return nullptr;
+        HIPCHECK(hipStreamSynchronize(s));
+        if (surv_hist.size() != nlist) surv_hist.assign(nlist, 0);
+        fetch_want.resize(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            ++surv_hist[sblist_host[fetch_surv[i].x >> 6]];
+            fetch_want[i] = {fetch_surv[i].x, i};
+        }
+        return fetch_rows(w, 0, n, n, s);
+    }
+
+    // TWO-PASS re-check (option screen_recheck2): the rows of the batch's survivors marked
+    // `phase` (1: pass A, each pair's k smallest lower bounds; 2: pass B, the others not above
+    // pass A's k-th exact distance; launch_tier_recheck) go into the slot's compact device
+    // rows, after those of the earlier phase; a row needed again (the same vector surviving for
+    // another query, or in both phases) is fetched once. The survivor -> row map is uploaded.
+    // Phase 1 returns false (need: the reserved candidate slots) when the candidate buffer
+    // overflowed: the caller re-runs the batch with a larger one.
     std::vector<uint8_t> fetch_mark;
     std::vector<uint32_t> fetch_rowmap;
     std::unordered_map<uint64_t, uint32_t> fetch_slot_row;
     uint32_t fetch_n = 0, fetch_rows_n = 0;
     bool fetch_rows_phase(SearchSlot& w, int phase, uint32_t& need, hipStream_t s) {
         if (phase == 1) {
-            uint32_t hc[vdbk::kCounters];
-            HIPCHECK(hipMemcpyAsync(hc, w.counters.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-            HIPCHECK(hipStreamSynchronize(s));
-            if (hc[vdbk::kCtrOvf]) {
-                need = hc[vdbk::kCtrCand];
-                return false;
-            }
-            fetch_n = hc[vdbk::kCtrSurv];
-            fetch_surv.resize(fetch_n);
-            if (fetch_n) HIPCHECK(hipMemcpyAsync(fetch_surv.data(), w.surv.p, (size_t)fetch_n * 8, hipMemcpyDeviceToHost, s));
+            if (!fetch_head(w, fetch_n, need, s)) return false;
             fetch_rows_n = 0;
             fetch_slot_row.clear();
             fetch_rowmap.assign(fetch_n, 0u);
@@ -1349,125 +1317,19 @@ struct vdb_ivf {
         if (n) HIPCHECK(hipMemcpyAsync(fetch_mark.data(), w.smark.p, n, hipMemcpyDeviceToHost, s));
         HIPCHECK(hipStreamSynchronize(s));
         if (surv_hist.size() != nlist) surv_hist.assign(nlist, 0);
-        // this phase's survivors: a slot read before maps to its row; new slots get rows j0 ..
+        // this phase's survivors: a slot fetched before maps to its row; new slots get rows j0 ..
         const uint32_t j0 = fetch_rows_n;
-        std::vector<uint32_t> todo;  // (a survivor per new slot)
+        fetch_want.clear();
         for (uint32_t i = 0; i < n; ++i) {
             if (fetch_mark[i] != (uint8_t)phase) continue;
             const uint64_t slot = fetch_surv[i].x;
             ++surv_hist[sblist_host[slot >> 6]];
-            auto it = fetch_slot_row.find(slot);
-            if (it != fetch_slot_row.end()) {
-                fetch_rowmap[i] = it->second;
-                continue;
-            }
-            const uint32_t j = fetch_rows_n++;
-            fetch_slot_row.emplace(slot, j);
-            fetch_rowmap[i] = j;
-            todo.push_back(i);
-        }
-        const uint32_t nn = fetch_rows_n - j0;
-        fetch_stage.host = true;
-        float* st = fetch_stage.ensure((size_t)std::max<uint32_t>(nn, 1) * dim);
-        if (row_uring && row_uring->capacity() < tier_row_qd) row_uring.reset();
-        if (!row_uring) row_uring.reset(new UringReader(tier_row_qd));
-        UringReader* const ur = row_uring.get();
-        const uint64_t row_bytes = (uint64_t)dim * 4;
-        const bool direct = tier_row_direct && home_fd_direct >= 0;
-        const uint32_t kQD = std::min(tier_row_qd, row_uring->capacity());
-        const uint64_t span = ((row_bytes + 4095) / 4096 + 1) * 4096;
-        char* bounce = nullptr;
-        if (direct) {
-            fetch_bounce.host = true;
-            bounce = fetch_bounce.ensure(kQD * span + 4096);
-            bounce = (char*)(((uintptr_t)bounce + 4095) & ~(uintptr_t)4095);
-        }
-        // cached lists' rows from HBM; the rest read in file order
-        cache_src_host.clear();
-        std::vector<uint32_t> order;  // (positions in todo)
-        order.reserve(todo.size());
-        for (uint32_t t = 0; t < (uint32_t)todo.size(); ++t) {
-            const uint64_t slot = fetch_surv[todo[t]].x;
-            const uint32_t l = sblist_host[slot >> 6];
-            if (tier_row_cache && !cache_off.empty() && cache_off[l] != kAbsent)
-                cache_src_host.push_back({(unsigned long long)(j0 + t),
-                                          (unsigned long long)(cache_off[l] * 64 + (slot - sblock_off[l] * 64))});
-            else
-                order.push_back(t);
-        }
-        std::sort(order.begin(), order.end(),
-                  [&](uint32_t x, uint32_t y) { return fetch_surv[todo[x]].x < fetch_surv[todo[y]].x; });
-        std::vector<uint32_t> slot_of(kQD), free_slots(kQD);
-        for (uint32_t b = 0; b < kQD; ++b) free_slots[b] = kQD - 1 - b;
-        std::vector<uint64_t> delta(kQD);
-        uint64_t bytes_read = 0;
-        const uint32_t nf = (uint32_t)order.size();
-        uint32_t next = 0, done = 0;
-        try {
-            while (done < nf) {
-                while (next < nf && next - done < kQD) {
-                    const uint32_t t = order[next];
-                    const uint64_t slot = fetch_surv[todo[t]].x;
-                    const uint32_t l = sblist_host[slot >> 6];
-                    const uint64_t off = file_off[l] + count[l] * 8 + (slot - sblock_off[l] * 64) * row_bytes;
-                    if (direct) {
-                        const uint32_t b = free_slots.back();
-                        free_slots.pop_back();
-                        const uint64_t g = dio_align;
-                        const uint64_t a0 = off / g * g, a1 = (off + row_bytes + g - 1) / g * g;
-                        delta[b] = off - a0;
-                        slot_of[b] = t;
-                        ur->read(home_fd_direct, bounce + (size_t)b * span, (uint32_t)(a1 - a0), a0, ((uint64_t)b << 32) | t);
-                        bytes_read += a1 - a0;
-                    } else {
-                        ur->read(home_fd, st + (size_t)t * dim, (uint32_t)row_bytes, off, t);
-                        bytes_read += row_bytes;
-                    }
-                    ++next;
-                }
-                for (const UringReader::Done& d : ur->wait(1)) {
-                    const uint32_t b = (uint32_t)(d.tag >> 32), t = (uint32_t)d.tag;
-                    const int64_t want = direct ? (int64_t)(delta[b] + row_bytes) : (int64_t)row_bytes;
-                    require(d.result >= want,
-                            "short read of a survivor row from the list file" +
-                                (d.result < 0 ? std::string(": ") + std::strerror((int)-d.result) : ""),
-                            VDB_ERR_STATE);
-                    if (direct) {
-                        std::memcpy(st + (size_t)t * dim, bounce + (size_t)b * span + delta[b], row_bytes);
-                        free_slots.push_back(b);
-                    }
-                    ++done;
-                }
-            }
-        } catch (...) {
-            ur->drain();
-            throw;
-        }
-        screen_rows_fetched += nf;
-        screen_row_bytes += (uint64_t)nf * row_bytes;
-        screen_rows_cached += cache_src_host.size();
-        file_bytes_read += bytes_read;
-        float* rows = slot_buf(w, w.srows, (size_t)std::max<uint32_t>(n, 1) * dp);
-        if (nn) {
-            if (dim == dp) {
-                HIPCHECK(hipMemcpyAsync(rows + (size_t)j0 * dp, st, (size_t)nn * row_bytes, hipMemcpyHostToDevice, s));
-            } else {
-                HIPCHECK(hipMemcpyAsync(fetch_dev.ensure((size_t)std::max<uint32_t>(n, 1) * dim), st, (size_t)nn * row_bytes,
-                                        hipMemcpyHostToDevice, s));
-                vdbk::launch_pad_rows(fetch_dev.p, nn, dim, dp, rows + (size_t)j0 * dp, s);
-                HIPCHECK(hipGetLastError());
-            }
-        }
-        if (!cache_src_host.empty()) {  // (overwrites those rows' unused staging content)
-            if (tier_call_used) HIPCHECK(hipEventSynchronize(tier_call_ev));
-            const uint32_t nc = (uint32_t)cache_src_host.size();
-            HIPCHECK(hipMemcpyAsync(cache_src.ensure(nc), cache_src_host.data(), (size_t)nc * sizeof(ulonglong2),
-                                    hipMemcpyHostToDevice, s));
-            vdbk::launch_gather_cache_rows(cache.p, d4, cache_src.p, nc, rows, s);
-            HIPCHECK(hipGetLastError());
+            const auto ins = fetch_slot_row.emplace(slot, fetch_rows_n);
+            fetch_rowmap[i] = ins.first->second;
+            if (ins.second) fetch_want.push_back({slot, fetch_rows_n++ - j0});
         }
         if (n) HIPCHECK(hipMemcpyAsync(w.rowmap.p, fetch_rowmap.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipStreamSynchronize(s));  // (the staging, the map and the cache's contents are reused later)
+        (void)fetch_rows(w, j0, fetch_rows_n - j0, n, s);  // (its closing sync covers the map's upload)
         return true;
     }
 
@@ -2525,7 +2387,7 @@ struct vdb_ivf {
                             break;
                         }
                     } else {
-                        fetched = fetch_survivor_rows(w, ccap, need, s);
+                        fetched = fetch_survivor_rows(w, need, s);
                         if (fetched) break;
                     }
                     const uint64_t grow = std::max<uint64_t>((uint64_t)need + need / 2, (uint64_t)ccap + 1024);

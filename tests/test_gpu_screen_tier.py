@@ -278,3 +278,62 @@ def test_screened_tier_row_cache_by_survivor_histogram(tmp_path):
         assert_same(*h.search(Q, nprobe=NPROBE, k=10), Dr, Ir)
         s1 = h.cache_stats()
         assert s1["screen_rows_cached"] > s0["screen_rows_cached"], (s0, s1)
+
+
+@pytest.fixture(scope="module")
+def row_read_case(tmp_path_factory):
+    """One saved index (dim 70: the fetched rows are padded) and its oracle results, shared by
+    every case of test_screened_tier_file_home_row_reads."""
+    dim = 70
+    X, Q, ids, o = data(dim, seed=9)
+    g = vdb.IVFFlatIndex(vdb.IVFFlatIndex.Config(dim, NLIST))
+    g.centroids = o.centroids
+    g.add(X, ids)
+    path = str(tmp_path_factory.mktemp("row_reads") / "index.vdb")
+    g.save(path)
+    del g
+    Dr, Ir = o.search(Q, NPROBE, 10)
+    return dim, Q, path, (need_blocks(o, Q, NPROBE) + 8) * block_bytes(dim), Dr, Ir
+
+
+@pytest.mark.parametrize("rc", [0, 1], ids=["file_rows", "row_cache"])
+@pytest.mark.parametrize("qd", [1, 256], ids=["qd1", "qd256"])
+@pytest.mark.parametrize("direct", [0, 1], ids=["buffered", "direct"])
+@pytest.mark.parametrize("recheck2", [0, 1], ids=["one_pass", "two_pass"])
+def test_screened_tier_file_home_row_reads(row_read_case, recheck2, direct, qd, rc):
+    """The survivors' rows read from the index file under every setting of the row reads: the
+    one-pass and the two-pass re-check, O_DIRECT and buffered, one read in flight and 256, with
+    and without the HBM row cache. Results are bit-identical to the oracle and the counters keep
+    their meaning: screen_rows_fetched counts the file reads, screen_row_bytes their rows'
+    bytes, file_bytes_read what the device delivered (buffered: the rows; O_DIRECT: each row's
+    aligned superset, at most 4095 bytes more on either side)."""
+    dim, Q, path, cache_bytes, Dr, Ir = row_read_case
+    h = vdb.IVFFlatIndex(vdb.IVFFlatIndex.Config(dim, NLIST))
+    h.set_option("screen_recheck2", recheck2)
+    h.set_option("tier_row_direct", direct)
+    h.set_option("tier_row_qd", qd)
+    h.set_option("tier_row_cache", rc)
+    h.set_option("list_cache_bytes", cache_bytes)
+    h.open_lists(path)
+    h.search(Q[:1], nprobe=NPROBE, k=10)  # (the shadow is built by streaming the file once)
+    for batch in (256, 5):
+        h.set_batch(batch)
+        s0 = h.cache_stats()
+        assert_same(*h.search(Q, nprobe=NPROBE, k=10), Dr, Ir)
+        s1 = h.cache_stats()
+        fetched = s1["screen_rows_fetched"] - s0["screen_rows_fetched"]
+        row_bytes = s1["screen_row_bytes"] - s0["screen_row_bytes"]
+        read = s1["file_bytes_read"] - s0["file_bytes_read"]
+        print(f"batch {batch}: fetched {fetched} row_bytes {row_bytes} file_bytes_read {read} "
+              f"cached {s1['screen_rows_cached'] - s0['screen_rows_cached']} o_direct {s1['o_direct']}")
+        assert s1["screen_row_bytes"] == s1["screen_rows_fetched"] * dim * 4, s1
+        if not rc:
+            assert s1["loads"] == 0, s1  # (no list is loaded: the file is read for rows only)
+            if direct and s1["o_direct"]:
+                assert row_bytes <= read <= row_bytes + 2 * 4095 * fetched, (s0, s1)
+            else:  # (also where the file system refuses O_DIRECT: the engine reads buffered)
+                assert read == row_bytes, (s0, s1)
+    st = h.cache_stats()
+    if rc:
+        assert st["screen_rows_cached"] > 0, st
+    assert h.survivor_histogram().sum() >= st["screen_rows_fetched"] + st["screen_rows_cached"] > 0, st
