@@ -548,10 +548,10 @@ int vdb_ivf_evict(vdb_ivf* h, uint32_t list) {
         // the list leaves the cache (evict_list_from_gpu, ivf_flat_index.cpp:447-471).
         std::lock_guard<std::mutex> g(h->mu);
         vdb_ivf* st = h->store_of(list);
-        if (!st->tiered() || st->cache_off[list] == vdb_ivf::kAbsent) return;
+        if (!st->tiered() || !st->lc.resident(list)) return;
         st->set_device();
         st->quiesce();
-        st->cache_free(list);
+        st->lc.evict(list);
         h->set_device();
     });
 }
@@ -565,7 +565,7 @@ uint64_t vdb_ivf_gpu_bytes(const vdb_ivf* h) {
     if (h->is_group()) return group::gpu_bytes(h, false);
     uint64_t b = 0;
     for (uint32_t l = 0; l < h->nlist; ++l) {
-        const bool resident = h->tiered() ? h->cache_off[l] != vdb_ivf::kAbsent : (bool)h->owned[l];
+        const bool resident = h->tiered() ? h->lc.resident(l) : (bool)h->owned[l];
         if (resident) b += h->count[l] * ((uint64_t)h->dim * 4 + 8);
     }
     return b;
@@ -781,12 +781,13 @@ int vdb_ivf_cache_stats(vdb_ivf* h, vdb_ivf_cache_stats_t* out) {
         else
             hs.push_back(h);
         for (vdb_ivf* m : hs) {
-            out->capacity_bytes += m->cache_blocks * vdb_ivf::block_bytes(m->dp);
-            out->resident_bytes += m->cache_used * vdb_ivf::block_bytes(m->dp);
-            out->loads += m->cache_loads;
-            out->evictions += m->cache_evictions;
-            out->bytes_loaded += m->cache_bytes_in;
-            for (uint32_t l = 0; l < m->nlist && m->tiered(); ++l) out->resident_lists += m->cache_off[l] != vdb_ivf::kAbsent;
+            const uint64_t bb = vdb_ivf::block_bytes(m->dp);
+            out->capacity_bytes += m->lc.capacity() * bb;
+            out->resident_bytes += m->lc.used() * bb;
+            out->loads += m->lc.loads();
+            out->evictions += m->lc.evictions();
+            out->bytes_loaded += m->lc.blocks_loaded() * bb;
+            out->resident_lists += m->lc.resident_lists();
             out->file_bytes_read += m->file_bytes_read;
             out->subbatches += m->tier_subbatches;
             out->prefetches += m->tier_prefetches;
@@ -853,7 +854,7 @@ int vdb_ivf_fill_row_cache(vdb_ivf* h, const uint64_t* weights) {
         if (!(h->tiered() && h->file_home() && h->tier_row_cache)) return;
         if (h->screen_stale) h->screen_update();  // (its build fills the cache itself)
         if (!h->screen_ready) return;
-        h->cache_reset();  // (refilled in the new order)
+        h->lc.reset(h->nlist, h->lc.capacity());  // (refilled in the new order)
         h->fill_row_cache();
     });
 }

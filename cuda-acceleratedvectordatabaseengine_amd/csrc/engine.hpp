@@ -41,6 +41,7 @@
 #include "../../include/vdb_ivf.h"
 #include "kernels.hpp"
 #include "floor.hpp"
+#include "list_cache.hpp"
 #include "row_reader.hpp"
 #include "uring.hpp"
 
@@ -414,17 +415,12 @@ struct vdb_ivf {
     // page-locked host memory and HBM holds a cache of whole lists. Before a batch is
     // planned, every list it probes is made resident (DMA of its blocks), evicting the
     // least recently used lists the batch does not probe; the scan reads the cache
-    // through the same directory (d_block_off), so the kernels are unchanged.
-    static constexpr uint64_t kAbsent = ~0ull;
-    uint64_t cache_blocks = 0;  // capacity in 64-vector blocks (0: tier off, the arena is in HBM)
+    // through the same directory (d_block_off), so the kernels are unchanged. Where the
+    // lists sit in the cache, which leave and how a call is cut: list_cache.hpp.
+    ListCache lc;  // (capacity 0: tier off, the arena is in HBM)
     DevBuf<float4> cache{true};
     DevBuf<uint64_t> cache_ids{true};
-    std::vector<uint64_t> cache_off;        // per list: cache block offset or kAbsent
-    std::vector<uint64_t> last_use;         // per list: batch tick of the last probe
-    std::map<uint64_t, uint64_t> free_ext;  // free cache extents: block offset -> blocks
-    uint64_t use_tick = 0, cache_used = 0;
-    uint64_t resident_n = 0, storable_n = 0;  // cached lists / non-empty lists stored here
-    uint64_t cache_loads = 0, cache_evictions = 0, cache_bytes_in = 0;
+    uint64_t storable_n = 0;  // non-empty lists stored here
     DevBuf<uint32_t> probe_stage;  // pinned: the batch's probes, read by the host
     DevBuf<uint64_t> dir_stage;    // pinned: directory upload source
     // Recorded after every cache load and directory upload, on the stream that made
@@ -1150,10 +1146,10 @@ struct vdb_ivf {
     std::vector<double> row_cache_weight;  // (empty: by size)
     std::vector<uint64_t> surv_hist;       // per list: survivor rows of the tier's screened batches
     void fill_row_cache() {
-        if (!cache_blocks) return;
+        if (!tiered()) return;
         std::vector<uint32_t> order;
         for (uint32_t l = 0; l < nlist; ++l)
-            if (owned[l] && count[l] && cache_off[l] == kAbsent) order.push_back(l);
+            if (owned[l] && count[l] && !lc.resident(l)) order.push_back(l);
         if (row_cache_weight.size() == nlist)
             std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
                 const double wx = row_cache_weight[x] / (double)count[x], wy = row_cache_weight[y] / (double)count[y];
@@ -1161,15 +1157,10 @@ struct vdb_ivf {
             });
         else
             std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return count[x] > count[y]; });
-        std::vector<std::pair<uint32_t, uint64_t>> loads;
+        std::vector<ListCache::Load> loads;
         for (uint32_t l : order) {
-            const uint64_t off = cache_alloc(list_blocks(l));
-            if (off == kAbsent) continue;  // (a smaller list may still fit)
-            cache_off[l] = off;
-            ++resident_n;
-            ++cache_loads;
-            cache_bytes_in += list_blocks(l) * block_bytes(dp);
-            loads.push_back({l, off});
+            const uint64_t off = lc.place(l, list_blocks(l));
+            if (off != ListCache::kAbsent) loads.push_back({l, off});  // (else a smaller list may still fit)
         }
         if (loads.empty()) return;
         load_lists(loads, stream);
@@ -1215,9 +1206,9 @@ struct vdb_ivf {
         file.reserve(fetch_want.size());
         for (const auto& sr : fetch_want) {
             const uint32_t l = sblist_host[sr.first >> 6];
-            if (tier_row_cache && !cache_off.empty() && cache_off[l] != kAbsent)
+            if (tier_row_cache && lc.resident(l))
                 cache_src_host.push_back({(unsigned long long)(row0 + sr.second),
-                                          (unsigned long long)(cache_off[l] * 64 + (sr.first - sblock_off[l] * 64))});
+                                          (unsigned long long)(lc.offset(l) * 64 + (sr.first - sblock_off[l] * 64))});
             else
                 file.push_back(sr);
         }
@@ -1384,54 +1375,15 @@ struct vdb_ivf {
         arena_blocks = blocks;
         block_off = new_off;
         owned = new_owned;
-        cache_reset();  // list contents or offsets changed: nothing cached stays valid
+        lc.reset(nlist, lc.capacity());  // list contents or offsets changed: nothing cached stays valid
     }
 
     // ---- list-cache tier ----
-    bool tiered() const { return cache_blocks > 0; }
+    bool tiered() const { return lc.capacity() > 0; }
     uint64_t list_blocks(uint32_t l) const { return cdiv(count[l], 64); }
     static uint64_t block_bytes(uint32_t dp_) { return 64ull * ((uint64_t)dp_ * 4 + 8); }
 
-    void cache_reset() {
-        cache_off.assign(nlist, kAbsent);
-        last_use.assign(nlist, 0);
-        free_ext.clear();
-        if (cache_blocks) free_ext[0] = cache_blocks;
-        cache_used = 0;
-        resident_n = 0;
-    }
-
-    uint64_t cache_alloc(uint64_t nb) {  // first fit
-        for (auto it = free_ext.begin(); it != free_ext.end(); ++it) {
-            if (it->second < nb) continue;
-            const uint64_t off = it->first, len = it->second;
-            free_ext.erase(it);
-            if (len > nb) free_ext[off + nb] = len - nb;
-            cache_used += nb;
-            return off;
-        }
-        return kAbsent;
-    }
-
-    void cache_free(uint32_t l) {
-        const uint64_t nb = list_blocks(l);
-        auto it = free_ext.emplace(cache_off[l], nb).first;
-        cache_off[l] = kAbsent;
-        cache_used -= nb;
-        --resident_n;
-        auto nx = std::next(it);
-        if (nx != free_ext.end() && it->first + it->second == nx->first) {
-            it->second += nx->second;
-            free_ext.erase(nx);
-        }
-        if (it != free_ext.begin()) {
-            auto pv = std::prev(it);
-            if (pv->first + pv->second == it->first) {
-                pv->second += it->second;
-                free_ext.erase(it);
-            }
-        }
-    }
+    ListSizes list_sizes() const { return ListSizes{count, owned}; }
 
     // Scan directory: home offsets, or cache offsets in the tier (absent lists: 0,
     // never read: a list is made resident before any batch that probes it is planned).
@@ -1442,7 +1394,7 @@ struct vdb_ivf {
             if (tier_ev_used) HIPCHECK(hipEventSynchronize(tier_ev));
             dir_stage.host = true;
             uint64_t* st = dir_stage.ensure(nlist);
-            for (uint32_t l = 0; l < nlist; ++l) st[l] = cache_off[l] == kAbsent ? 0 : cache_off[l];
+            for (uint32_t l = 0; l < nlist; ++l) st[l] = lc.resident(l) ? lc.offset(l) : 0;
             src = st;
         }
         HIPCHECK(hipMemcpyAsync(d_block_off.ensure(nlist), src, nlist * 8, hipMemcpyHostToDevice, s));
@@ -1455,105 +1407,20 @@ struct vdb_ivf {
         tier_ev_used = true;
     }
 
-    // Cache residency planning. Lists that are empty or not stored here are never
-    // cached. `want` (unique lists) must all be resident afterwards; lists marked in
-    // `protect` are never evicted; a victim is the cached list whose next use (rank()
-    // : larger = later, UINT64_MAX = never) is furthest away, then the least recently
-    // used. Returns false, changing nothing, when `want` cannot be placed (over capacity,
-    // or fragmentation with `repack` off); with `repack` every cached list outside `want`
-    // is dropped and `want` is re-laid from offset 0 when fragmentation blocks a load.
-    // The cache map changes at once; the data moves with load_lists, in stream order.
-    template <class Rank>
-    bool plan_loads(const std::vector<uint32_t>& want, const std::vector<uint8_t>& protect, Rank&& rank, bool repack,
-                    std::vector<std::pair<uint32_t, uint64_t>>& loads) {
-        loads.clear();
-        uint64_t need = 0;
-        std::vector<uint32_t> miss;
-        for (uint32_t l : want) {
-            need += list_blocks(l);
-            if (cache_off[l] == kAbsent) miss.push_back(l);
-        }
-        if (need > cache_blocks) return false;
-        if (miss.empty()) return true;
-        auto by_size = [&](uint32_t a, uint32_t b) { return count[a] != count[b] ? count[a] > count[b] : a < b; };
-        std::vector<uint32_t> victims;
-        for (uint32_t l = 0; l < nlist; ++l)
-            if (cache_off[l] != kAbsent && !protect[l]) victims.push_back(l);
-        std::vector<uint64_t> rk(nlist, 0);
-        for (uint32_t v : victims) rk[v] = rank(v);
-        std::sort(victims.begin(), victims.end(), [&](uint32_t a, uint32_t b) {
-            if (rk[a] != rk[b]) return rk[a] > rk[b];
-            return last_use[a] != last_use[b] ? last_use[a] < last_use[b] : a < b;
-        });
-        // dry run on a copy of the extent map, so a failed plan changes nothing
-        const std::map<uint64_t, uint64_t> free_save = free_ext;
-        const std::vector<uint64_t> off_save = cache_off;
-        const uint64_t used_save = cache_used, res_save = resident_n;
-        std::sort(miss.begin(), miss.end(), by_size);
-        size_t vi = 0;
-        uint64_t evicted = 0;
-        for (size_t m = 0; m < miss.size(); ++m) {
-            const uint32_t l = miss[m];
-            uint64_t off;
-            while ((off = cache_alloc(list_blocks(l))) == kAbsent && vi < victims.size()) {
-                cache_free(victims[vi++]);
-                ++evicted;
-            }
-            if (off == kAbsent) {
-                if (!repack) {  // undo: the caller falls back to a later, synchronous load
-                    free_ext = free_save;
-                    cache_off = off_save;
-                    cache_used = used_save;
-                    resident_n = res_save;
-                    loads.clear();
-                    return false;
-                }
-                // fragmented: keep only `want`, packed from offset 0 (they fit)
-                for (uint32_t v = 0; v < nlist; ++v)
-                    if (cache_off[v] != kAbsent) cache_free(v);
-                miss = want;
-                std::sort(miss.begin(), miss.end(), by_size);
-                loads.clear();
-                m = (size_t)-1;
-                continue;
-            }
-            cache_off[l] = off;
-            ++resident_n;
-            loads.push_back({l, off});
-        }
-        cache_evictions += evicted;
-        cache_loads += loads.size();
-        for (auto& ld : loads) cache_bytes_in += list_blocks(ld.first) * block_bytes(dp);
-        return true;
-    }
-
-    // Unique cacheable lists of a probe array.
-    std::vector<uint32_t> cacheable(const uint32_t* lists, size_t n, std::vector<uint8_t>& mark) {
-        std::vector<uint32_t> out;
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t l = lists[i];
-            if (l >= nlist || mark[l] || !owned[l] || count[l] == 0) continue;
-            mark[l] = 1;
-            out.push_back(l);
-        }
-        for (uint32_t l : out) mark[l] = 0;
-        return out;
-    }
-
     // Make `lists` resident on stream s (warmup and single lists): LRU eviction.
     // False if together they exceed the cache.
     bool make_resident(const uint32_t* lists, size_t n, hipStream_t s) {
-        ++use_tick;
+        const ListSizes sz = list_sizes();
         std::vector<uint8_t> mark(nlist, 0);
-        const std::vector<uint32_t> want = cacheable(lists, n, mark);
-        for (uint32_t l : want) last_use[l] = use_tick;
+        const std::vector<uint32_t> want = sz.unique(lists, n, mark);
+        lc.touch(want);
         std::vector<uint8_t> protect(nlist, 0);
         for (uint32_t l : want) protect[l] = 1;
         bool miss = false;
-        for (uint32_t l : want) miss |= cache_off[l] == kAbsent;
+        for (uint32_t l : want) miss |= !lc.resident(l);
         if (miss) quiesce();  // searches on other streams may still read the lists evicted below
-        std::vector<std::pair<uint32_t, uint64_t>> loads;
-        if (!plan_loads(want, protect, [](uint32_t) { return uint64_t(0); }, true, loads)) return false;
+        std::vector<ListCache::Load> loads;
+        if (!lc.plan_loads(want, protect, sz, [](uint32_t) { return uint64_t(0); }, true, loads)) return false;
         if (loads.empty()) return true;
         load_lists(loads, s);
         upload_scan_directory(s);
@@ -1579,7 +1446,7 @@ struct vdb_ivf {
     // each chunk's ids and rows are read (io_uring, up to kStages chunks in flight) into
     // a page-locked staging buffer, copied to HBM, padded to dp and interleaved into the
     // cache's block layout; a buffer is refilled once its copies have landed.
-    void load_lists(const std::vector<std::pair<uint32_t, uint64_t>>& loads, hipStream_t s,
+    void load_lists(const std::vector<ListCache::Load>& loads, hipStream_t s,
                     float4* dst_v = nullptr, uint64_t* dst_i = nullptr) {
         float4* const tv = dst_v ? dst_v : cache.p;  // (the cache, or a caller's block buffer)
         uint64_t* const ti = dst_i ? dst_i : cache_ids.p;
@@ -1686,7 +1553,7 @@ struct vdb_ivf {
             // load may be partly written), so the next load starts clean.
             uring->drain();
             for (Stage& st : stages) st.reads = 0;
-            cache_reset();
+            lc.reset(nlist, lc.capacity());
             throw;
         }
     }
@@ -1765,7 +1632,7 @@ struct vdb_ivf {
         owned = own;
         rank = shard_file ? hdr[3] : 0;
         world = shard_file ? hdr[4] : 1;
-        cache_reset();
+        lc.reset(nlist, lc.capacity());
         upload_directory();
     }
 
@@ -1778,14 +1645,13 @@ struct vdb_ivf {
         require(nb > 0 || !file_home(), "lists served from a file need the list-cache tier", VDB_ERR_STATE);
         cache.release();
         cache_ids.release();
-        cache_blocks = 0;
+        lc.reset(nlist, 0);
         if (!file_home() && (nb > 0) != arena.host) relayout(count, owned, nb > 0);  // moves the arena
-        cache_blocks = nb;
         if (nb) {  // one slack block: the scan prefetches past a segment's end
             cache.ensure((nb + 1) * d4 * 64);
             cache_ids.ensure((nb + 1) * 64);
         }
-        cache_reset();
+        lc.reset(nlist, nb);
         upload_directory();
     }
 
@@ -2057,7 +1923,7 @@ struct vdb_ivf {
         if (file_home()) {  // nothing in memory to move: the file holds every list
             quiesce();
             owned = new_owned;
-            cache_reset();
+            lc.reset(nlist, lc.capacity());
         } else {
             relayout(count, new_owned);
         }
@@ -2507,6 +2373,8 @@ struct vdb_ivf {
     //  * a victim is the cached list whose next use in the call is furthest away (not
     //    used again: first), then the least recently used; sub-batch i's lists (and i+1's)
     //    are never evicted while i runs.
+    // The cut, the victim order and the placement are list_cache.hpp's; here are the data
+    // movement and its ordering.
     // (qbase: the call-global index of d_q's first query, for the stale-slot semantics)
     void search_tiered(SearchSlot& w, const float* d_q, uint32_t n, uint32_t P, uint32_t k, float* d_dist,
                        uint64_t* d_ids, hipStream_t s, const uint32_t* req_start, uint32_t qbase = 0) {
@@ -2521,51 +2389,21 @@ struct vdb_ivf {
             HIPCHECK(hipMemcpyAsync(hp + (size_t)b0 * P, w.probes.p, (size_t)B * P * 4, hipMemcpyDeviceToHost, s));
         }
         HIPCHECK(hipStreamSynchronize(s));
-        // 2. sub-batches whose lists fit the cache
-        std::vector<uint8_t> qmark(nlist, 0), umark(nlist, 0);  // (a query's lists, the sub-batch's lists)
-        std::vector<uint32_t> sb_begin;
-        std::vector<std::vector<uint32_t>> U;
-        uint64_t blocks = 0;
-        for (uint32_t q = 0; q < n; ++q) {
-            const std::vector<uint32_t> ql = cacheable(hp + (size_t)q * P, P, qmark);
-            uint64_t qb = 0, add = 0;
-            for (uint32_t l : ql) {
-                qb += list_blocks(l);
-                if (!umark[l]) add += list_blocks(l);
-            }
-            require(qb <= cache_blocks, "list_cache_bytes cannot hold the lists one query probes", VDB_ERR_OUT_OF_MEMORY);
-            // half the cache per sub-batch: the next one's lists can load beside it
-            if (U.empty() || q - sb_begin.back() >= bmax || blocks + add > cache_blocks / 2) {
-                if (!U.empty())
-                    for (uint32_t l : U.back()) umark[l] = 0;
-                sb_begin.push_back(q);
-                U.emplace_back();
-                blocks = 0;
-            }
-            for (uint32_t l : ql)
-                if (!umark[l]) {
-                    umark[l] = 1;
-                    U.back().push_back(l);
-                    blocks += list_blocks(l);
-                }
+        // 2. sub-batches whose lists fit the cache, and each list's uses for the next-use ranks
+        const ListSizes sz = list_sizes();
+        SubBatches sb;
+        try {
+            sb = cut_subbatches(hp, n, P, bmax, sz, lc);
+        } catch (const QueryOverCapacity&) {
+            throw VdbError(VDB_ERR_OUT_OF_MEMORY, "list_cache_bytes cannot hold the lists one query probes");
         }
-        const size_t nsb = U.size();
-        sb_begin.push_back(n);
-        // next-use ranks: for each list the sub-batches that use it, in order
-        std::vector<std::vector<uint32_t>> uses(nlist);
+        const size_t nsb = sb.size();
+        const std::vector<std::vector<uint32_t>>& U = sb.lists;
+        const std::vector<uint32_t>& sb_begin = sb.begin;
         bool miss = false;
-        for (size_t b = 0; b < nsb; ++b)
-            for (uint32_t l : U[b]) {
-                uses[l].push_back((uint32_t)b);
-                miss |= cache_off[l] == kAbsent;
-            }
-        auto rank_after = [&](size_t cur) {
-            return [&, cur](uint32_t l) -> uint64_t {
-                const auto& u = uses[l];
-                auto it = std::upper_bound(u.begin(), u.end(), (uint32_t)cur);
-                return it == u.end() ? ~0ull : (uint64_t)*it;
-            };
-        };
+        for (const auto& u : U)
+            for (uint32_t l : u) miss |= !lc.resident(l);
+        auto rank_after = [&](size_t cur) { return [&sb, cur](uint32_t l) { return next_use(sb, l, cur); }; };
         if (miss) quiesce();  // searches on other streams may still read lists evicted below
         if (!copy_stream) {
             HIPCHECK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
@@ -2575,7 +2413,7 @@ struct vdb_ivf {
         }
         // 3. sub-batches in order, each next one's lists loaded while the current one scans
         std::vector<uint8_t> protect(nlist, 0);
-        std::vector<std::pair<uint32_t, uint64_t>> loads;
+        std::vector<ListCache::Load> loads;
         bool prefetched = false;
         for (size_t b = 0; b < nsb; ++b) {
             const uint32_t b0 = sb_begin[b], B = sb_begin[b + 1] - b0;
@@ -2583,7 +2421,7 @@ struct vdb_ivf {
                 HIPCHECK(hipStreamWaitEvent(s, load_ev, 0));
             } else {  // load on s itself, after the previous sub-batch in stream order
                 for (uint32_t l : U[b]) protect[l] = 1;
-                const bool ok = plan_loads(U[b], protect, rank_after(b), true, loads);
+                const bool ok = lc.plan_loads(U[b], protect, sz, rank_after(b), true, loads);
                 for (uint32_t l : U[b]) protect[l] = 0;
                 require(ok, "list_cache_bytes cannot hold the lists one sub-batch probes", VDB_ERR_OUT_OF_MEMORY);
                 if (!loads.empty()) {
@@ -2592,8 +2430,7 @@ struct vdb_ivf {
                     ++tier_sync_loads;
                 }
             }
-            ++use_tick;
-            for (uint32_t l : U[b]) last_use[l] = use_tick;
+            lc.touch(U[b]);
             EventSet* ev = prof ? &next_events() : nullptr;
             if (ev) HIPCHECK(hipEventRecord(ev->begin, s));
             stage_queries(w, d_q + (size_t)b0 * dim, B, s);
@@ -2607,7 +2444,7 @@ struct vdb_ivf {
             if (b + 1 < nsb) {
                 for (uint32_t l : U[b]) protect[l] = 1;
                 for (uint32_t l : U[b + 1]) protect[l] = 1;
-                const bool ok = plan_loads(U[b + 1], protect, rank_after(b + 1), false, loads);
+                const bool ok = lc.plan_loads(U[b + 1], protect, sz, rank_after(b + 1), false, loads);
                 for (uint32_t l : U[b]) protect[l] = 0;
                 for (uint32_t l : U[b + 1]) protect[l] = 0;
                 if (ok) {
@@ -2768,7 +2605,7 @@ struct vdb_ivf {
             end_call(w, s);
             return;
         }
-        if (tiered() && resident_n < storable_n && !screen_serves(k, P)) {  // (every stored list cached: the plain path)
+        if (tiered() && lc.resident_lists() < storable_n && !screen_serves(k, P)) {  // (every stored list cached: the plain path)
             search_tiered(w, d_q, n, P, k, d_dist, d_ids, s, req_start);
             end_call(w, s);
             return;
@@ -2790,7 +2627,7 @@ struct vdb_ivf {
         slot_buf(w, w.xrec, vdb_rank_record_bytes(n, k));
         float* rd = rec_dist(w);
         uint64_t* ri = rec_ids(w, n, k);
-        if (tiered() && resident_n < storable_n && !screen_serves(k, P)) {
+        if (tiered() && lc.resident_lists() < storable_n && !screen_serves(k, P)) {
             search_tiered(w, d_q, n, P, k, rd, ri, s, req_start);
             return;
         }

@@ -198,6 +198,76 @@ def test_tier_pipeline_file_home_next_use_and_prefetch(tmp_path):
     assert h.cache_stats()["file_bytes_read"] - before <= int(blocks.sum()) * 64 * (D * 4 + 8) * len(Q)
 
 
+COUNTERS = ("loads", "evictions", "bytes_loaded", "resident_lists", "resident_bytes", "subbatches", "prefetches",
+            "sync_loads")
+# cache_stats() after each step of counter_sequence(), measured by running this same test on
+# the commit before the cache map moved to csrc/list_cache.hpp (the map inside struct vdb_ivf),
+# on an MI355X. They are functions of the host's placement, victim order and sub-batch cut
+# and of the bit-exact probes only, so any change of that policy shows here; the host home
+# and the file home gave the same figures (the data path does not enter).
+COUNTERS_EXPECTED = [
+    (485, 475, 20258304, 10, 422400, 197, 192, 2),     # search, batch 64
+    (491, 480, 20477952, 11, 422400, 197, 192, 2),     # warmup of six lists
+    (735, 725, 30750720, 10, 422400, 294, 285, 3),     # search, batch 7
+    (735, 725, 30750720, 8, 321024, 294, 285, 3),      # two lists evicted
+    (1228, 1217, 51448320, 9, 388608, 491, 475, 7),    # search, batch 32
+]
+
+
+def counter_sequence(home, tmp_path):
+    """A fixed sequence of calls on a cache of about a third of the lists; returns the
+    integer counters of cache_stats() after each step."""
+    dim, nlist, nprobe, k = 16, 32, 4, 10
+    X, Q, ids = oracle.reference_test_data(4000, 200, dim, seed=11)
+    o = oracle.OracleIndex(dim, nlist, 0)
+    o.train(X[:2000])
+    o.add(X, ids)
+    blocks = np.array([(o.list_count(l) + 63) // 64 for l in range(nlist)])
+    cap = int(blocks.sum()) // 3
+    assert cap >= max(int(blocks[o.select_nprobe(q, nprobe)].sum()) for q in Q)
+    g = vdb.IVFFlatIndex(vdb.IVFFlatIndex.Config(dim, nlist))
+    g.set_option("screen", 0)
+    g.centroids = o.centroids
+    g.add(X, ids)
+    if home == "file":
+        path = str(tmp_path / "counters.vdb")
+        g.save(path)
+        g = vdb.IVFFlatIndex(vdb.IVFFlatIndex.Config(dim, nlist))
+        g.set_option("screen", 0)
+        g.set_option("list_cache_bytes", cap * 64 * (64 * 4 + 8))   # (16 dims pad to dp = 64)
+        g.open_lists(path)
+    else:
+        g.set_option("list_cache_bytes", cap * 64 * (64 * 4 + 8))
+    Dr, Ir = o.search(Q, nprobe, k)
+    snaps = []
+
+    def snap():
+        st = g.cache_stats()
+        snaps.append(tuple(int(st[c]) for c in COUNTERS))
+
+    def search(batch, lo, hi):
+        g.set_batch(batch)
+        assert_same(*g.search(Q[lo:hi], nprobe=nprobe, k=k), Dr[lo:hi], Ir[lo:hi])
+        snap()
+
+    search(64, 0, 200)
+    g.warmup_lists([int(l) for l in np.random.default_rng(3).permutation(nlist)[:6]])
+    snap()
+    search(7, 50, 150)
+    for l in o.select_nprobe(Q[149], nprobe)[:2]:           # (probed by the last query: cached)
+        g.evict_list(int(l))
+    snap()
+    search(32, 0, 200)
+    return snaps
+
+
+@pytest.mark.parametrize("home", ["host", "file"])
+def test_cache_counters_equal_the_recorded_ones(tmp_path, home):
+    snaps = counter_sequence(home, tmp_path)
+    print(home, snaps)
+    assert snaps == COUNTERS_EXPECTED
+
+
 def test_tier_concurrent_streams_under_eviction():
     """Three searches in flight on three streams while the cache evicts and reloads
     (host-memory home): every stream's results equal the oracle's (a search on
