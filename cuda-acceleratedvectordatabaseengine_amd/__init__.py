@@ -113,6 +113,9 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_get_centroids": (ctypes.c_int, [vp, vp]),
         "vdb_ivf_add": (ctypes.c_int, [vp, vp, vp, u64]),
         "vdb_ivf_add_device": (ctypes.c_int, [vp, vp, vp, u64]),
+        "vdb_ivf_remove_ids": (ctypes.c_int, [vp, vp, u64, ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_remove_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_ivf_search": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp]),
         "vdb_ivf_search_device": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "vdb_ivf_set_shard": (ctypes.c_int, [vp, u32, u32]),
@@ -318,6 +321,21 @@ class IVFFlatIndex:
 
     def add_device(self, vec_ptr: int, ids_ptr: int, n: int):
         _check(lib().vdb_ivf_add_device(self._h, ctypes.c_void_p(vec_ptr), ctypes.c_void_p(ids_ptr), n))
+
+    def remove_ids(self, ids) -> int:
+        """Remove every stored row whose id is listed (vdb_ivf_remove_ids; not in the reference).
+        Returns the number of rows removed; the index is afterwards the one built by adding the
+        surviving rows in their original order."""
+        i = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        gone = ctypes.c_uint64(0)
+        _check(lib().vdb_ivf_remove_ids(self._h, _ptr(i), i.shape[0], ctypes.byref(gone)))
+        return int(gone.value)
+
+    def remove_last_timing(self) -> dict:
+        """The calling thread's latest remove_ids by step (vdb_remove_last_timing)."""
+        a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
+        _check(lib().vdb_remove_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
+        return {"mark_ms": a.value, "plan_ms": b.value, "compact_ms": c.value, "rows_kept": r.value}
 
     def assign_device(self, vec_ptr: int, n: int, lists_ptr: int):
         """Exact nearest-centroid list of n device rows into u32 lists_ptr (assign_to_lists, cpp:259-295)."""

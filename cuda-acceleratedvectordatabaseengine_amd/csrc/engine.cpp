@@ -4,6 +4,9 @@
 
 #include <cmath>
 
+#include "remove.hpp"
+#include "remove_plan.hpp"
+
 namespace vdbe {
 thread_local std::string g_last_error;
 
@@ -15,6 +18,7 @@ void add_device(vdb_ivf* g, const float* d_v, const uint64_t* d_ids, const uint3
 uint64_t gpu_bytes(const vdb_ivf* g, bool allocated);
 void set_option(vdb_ivf* g, const std::string& name, int64_t value);
 void synchronize(vdb_ivf* g);
+uint64_t remove_ids(vdb_ivf* g, const std::vector<uint64_t>& sorted);
 }  // namespace group
 
 // Calls that act on one device's shard have no group meaning.
@@ -207,6 +211,33 @@ int vdb_ivf_add_to_lists_device(vdb_ivf* h, const float* d_v, const uint64_t* d_
         h->append(h->padded_rows(d_v, n, tmp), d_ids, d_lists, n);
         HIPCHECK(hipStreamSynchronize(h->stream));
     });
+}
+
+int vdb_ivf_remove_ids(vdb_ivf* h, const uint64_t* ids, uint64_t n, uint64_t* removed) {
+    return guarded([&] {
+        require(h && (ids || n == 0), "null argument");  // (before any device call)
+        if (removed) *removed = 0;
+        require(n < (1ull << 31), "more than 2^31 - 1 ids in one remove", VDB_ERR_UNSUPPORTED);
+        std::lock_guard<std::mutex> g(h->mu);
+        // A rank cannot see ids in lists it does not store, and the ranks' list sizes must
+        // stay equal for attach_comm: a shard refuses, untouched (a group removes on every member).
+        require(h->is_group() || (h->world == 1 && h->comm_world == 1),
+                "remove_ids is not available on a sharded handle (set_shard / plan_shard / a shard file / "
+                "attach_comm with world > 1)",
+                VDB_ERR_UNSUPPORTED);
+        h->set_device();
+        const std::vector<uint64_t> sorted = remove_sorted_ids(ids, n);
+        const uint64_t gone = h->is_group() ? group::remove_ids(h, sorted) : remove_ids(*h, sorted, nullptr);
+        if (removed) *removed = gone;
+    });
+}
+
+int vdb_remove_last_timing(double* mark_ms, double* plan_ms, double* compact_ms, uint64_t* rows_kept) {
+    if (mark_ms) *mark_ms = g_remove_timing.mark_ms;
+    if (plan_ms) *plan_ms = g_remove_timing.plan_ms;
+    if (compact_ms) *compact_ms = g_remove_timing.compact_ms;
+    if (rows_kept) *rows_kept = g_remove_timing.rows_kept;
+    return VDB_OK;
 }
 
 int vdb_ivf_plan_shard(vdb_ivf* h, uint32_t rank, uint32_t world, const uint64_t* final_sizes) {

@@ -20,6 +20,8 @@
 
 #include <set>
 
+#include "remove.hpp"
+
 namespace vdbe {
 namespace {
 
@@ -200,6 +202,47 @@ void add_device(vdb_ivf* g, const float* d_v, const uint64_t* d_ids, const uint3
         }
     });
     sync_counts(g);
+}
+
+// remove_ids: every member removes from the lists it stores; every member counts every list,
+// so the owners' per-list removed counts are then applied to the other members' global
+// count[] and total before sync_counts. Ownership does not change; an emptied list stays placed.
+uint64_t remove_ids(vdb_ivf* g, const std::vector<uint64_t>& sorted) {
+    DeviceGuard dg;
+    const size_t M = g->members.size();
+    const uint32_t L = g->nlist;
+    std::vector<std::vector<uint64_t>> per(M, std::vector<uint64_t>(L, 0));
+    std::exception_ptr err;
+    try {
+        for_members(g, [&](size_t m) { vdbe::remove_ids(*g->members[m], sorted, &per[m]); });
+    } catch (...) {
+        err = std::current_exception();  // (the members that did remove are still accounted for below)
+    }
+    std::vector<uint64_t> gone(L, 0);
+    uint64_t sum = 0;
+    for (size_t m = 0; m < M; ++m)
+        for (uint32_t l = 0; l < L; ++l) {
+            gone[l] += per[m][l];
+            sum += per[m][l];
+        }
+    if (sum) {
+        for (size_t m = 0; m < M; ++m) {
+            vdb_ivf& mb = *g->members[m];
+            uint64_t others = 0;
+            for (uint32_t l = 0; l < L; ++l) {
+                const uint64_t d = gone[l] - per[m][l];  // rows of list l removed on other members
+                mb.count[l] -= d;
+                others += d;
+            }
+            if (!others) continue;
+            mb.total -= others;
+            mb.set_device();
+            mb.upload_directory();  // (the global counts decide emptiness in its scans)
+        }
+        sync_counts(g);
+    }
+    if (err) std::rethrow_exception(err);
+    return sum;
 }
 
 uint64_t gpu_bytes(const vdb_ivf* g, bool allocated) {

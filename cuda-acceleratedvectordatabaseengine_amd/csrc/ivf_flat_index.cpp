@@ -48,6 +48,12 @@ void IVFFlatIndex::add(const float* vectors, const uint64_t* ids, uint64_t n_vec
     ok(vdb_ivf_add(h_, vectors, ids, n_vectors), "add");
 }
 
+uint64_t IVFFlatIndex::remove(const uint64_t* ids, uint64_t n_ids) {
+    uint64_t removed = 0;
+    ok(vdb_ivf_remove_ids(h_, ids, n_ids, &removed), "remove");
+    return removed;
+}
+
 void IVFFlatIndex::search(const float* queries, uint32_t n_queries, const SearchParams& params, float* distances,
                           uint64_t* indices) {
     ok(vdb_ivf_search(h_, queries, n_queries, params.nprobe, params.k, distances, indices), "search");

@@ -48,6 +48,10 @@ public:
 
     void train(const float* vectors, uint64_t n_vectors);
     void add(const float* vectors, const uint64_t* ids, uint64_t n_vectors);
+    // Not in the reference (it cannot delete): removes every stored row whose id is listed
+    // (vdb_ivf_remove_ids) and returns how many went; the index is afterwards the one built
+    // by adding the surviving rows in their original order.
+    uint64_t remove(const uint64_t* ids, uint64_t n_ids);
     void search(const float* queries, uint32_t n_queries, const SearchParams& params, float* distances,
                 uint64_t* indices);
     // Declared but never defined in the reference: here request i searches the single

@@ -137,6 +137,28 @@ int vdb_ivf_add_to_lists(vdb_ivf* index, const float* vectors, const uint64_t* i
 int vdb_ivf_assign_device(vdb_ivf* index, const float* d_vectors, uint64_t n, uint32_t* d_lists);
 int vdb_ivf_add_to_lists_device(vdb_ivf* index, const float* d_vectors, const uint64_t* d_ids,
                                 const uint32_t* d_lists, uint64_t n);
+/* Remove every stored row whose id is one of ids[0..n) (host array). All rows carrying a
+ * listed id go (an index may hold an id more than once); ids that are not stored, and
+ * repeats within ids[], are ignored. The surviving rows of every list keep their order, so
+ * the handle is afterwards indistinguishable from one given the same centroids and the
+ * surviving rows in their original add order. *removed (may be NULL) receives the number of rows
+ * removed. Centroids are unchanged; a list may become empty.
+ * No counterpart in the reference (it cannot delete). The lists are compacted on the device
+ * into a fresh arena (peak memory old + new arena, the cost class of one add; the rows never
+ * travel through the host); searches in flight are quiesced first, as by add, and the next
+ * search rebuilds the screen. When n == 0 or no stored row matches, nothing is reallocated or
+ * rebuilt. Pad slots are never matched, whatever ids[] holds. n >= 2^31: VDB_ERR_UNSUPPORTED.
+ * Lists served from a file (vdb_ivf_open_lists): VDB_ERR_STATE, read-only as for add. If the
+ * fresh arena cannot be allocated: VDB_ERR_OUT_OF_MEMORY, the lists unchanged. A group handle
+ * removes on every member (*removed is the sum; list ownership does not change). A sharded
+ * handle (world > 1: vdb_ivf_set_shard, vdb_ivf_plan_shard, an opened shard file, an attached
+ * communicator) gives VDB_ERR_UNSUPPORTED and is left untouched: a rank cannot see ids in
+ * lists it does not store, and the ranks' list sizes must stay equal for vdb_ivf_attach_comm. */
+int vdb_ivf_remove_ids(vdb_ivf* index, const uint64_t* ids, uint64_t n, uint64_t* removed);
+/* Diagnostics: the calling thread's latest vdb_ivf_remove_ids on a single-device handle, by
+ * step: the mark kernel and the compact kernel (HIP events), the host plan between them, and
+ * the rows the compact pass moved. Any pointer may be NULL. */
+int vdb_remove_last_timing(double* mark_ms, double* plan_ms, double* compact_ms, uint64_t* rows_kept);
 /* Persist / restore centroids and lists (IVFFlatIndex::save/load, engine/ivf_flat_index.h:66-67,
  * declared but never defined in the reference; this engine's own file format). */
 int vdb_ivf_save(vdb_ivf* index, const char* path);
