@@ -113,10 +113,14 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_get_centroids": (ctypes.c_int, [vp, vp]),
         "vdb_ivf_add": (ctypes.c_int, [vp, vp, vp, u64]),
         "vdb_ivf_add_device": (ctypes.c_int, [vp, vp, vp, u64]),
+        "vdb_ivf_add_to_lists": (ctypes.c_int, [vp, vp, vp, vp, u64]),
         "vdb_ivf_remove_ids": (ctypes.c_int, [vp, vp, u64, ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_remove_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_ivf_search": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp]),
+        "vdb_ivf_search_filtered": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, u64, ctypes.c_int, vp, vp]),
+        "vdb_filter_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_ivf_search_device": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "vdb_ivf_set_shard": (ctypes.c_int, [vp, u32, u32]),
         "vdb_ivf_plan_shard": (ctypes.c_int, [vp, u32, u32, vp]),
@@ -322,6 +326,15 @@ class IVFFlatIndex:
     def add_device(self, vec_ptr: int, ids_ptr: int, n: int):
         _check(lib().vdb_ivf_add_device(self._h, ctypes.c_void_p(vec_ptr), ctypes.c_void_p(ids_ptr), n))
 
+    def add_to_lists(self, vectors: np.ndarray, ids: np.ndarray, lists: np.ndarray):
+        """Append host rows to explicitly given lists, input order kept per list (vdb_ivf_add_to_lists)."""
+        v = np.ascontiguousarray(vectors, dtype=np.float32).reshape(-1, self.dimension)
+        i = np.ascontiguousarray(ids, dtype=np.uint64)
+        l = np.ascontiguousarray(lists, dtype=np.uint32)
+        if i.shape[0] != v.shape[0] or l.shape[0] != v.shape[0]:
+            raise ValueError("vectors, ids and lists differ in length")
+        _check(lib().vdb_ivf_add_to_lists(self._h, _ptr(v), _ptr(i), _ptr(l), v.shape[0]))
+
     def remove_ids(self, ids) -> int:
         """Remove every stored row whose id is listed (vdb_ivf_remove_ids; not in the reference).
         Returns the number of rows removed; the index is afterwards the one built by adding the
@@ -368,6 +381,30 @@ class IVFFlatIndex:
         I = np.empty((n, k), dtype=np.uint64)
         _check(lib().vdb_ivf_search(self._h, _ptr(q), n, nprobe, k, _ptr(D), _ptr(I)))
         return D, I
+
+    def search_filtered(self, queries: np.ndarray, params: "IVFFlatIndex.SearchParams | None" = None, *,
+                        ids, include: bool = False, nprobe: int | None = None, k: int | None = None):
+        """search over the stored rows an id filter allows (vdb_ivf_search_filtered; not in the
+        reference). include=False: every row whose id is not in `ids`; include=True: only rows
+        whose id is. Returns (distances, indices) like search: the result search gives on an
+        index holding only the allowed rows."""
+        p = params or IVFFlatIndex.SearchParams()
+        nprobe = p.nprobe if nprobe is None else nprobe
+        k = p.k if k is None else k
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
+        f = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        n = q.shape[0]
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.uint64)
+        _check(lib().vdb_ivf_search_filtered(self._h, _ptr(q), n, nprobe, k, _ptr(f), f.shape[0],
+                                             1 if include else 0, _ptr(D), _ptr(I)))
+        return D, I
+
+    def filter_last_timing(self) -> dict:
+        """The calling thread's latest search_filtered by step (vdb_filter_last_timing)."""
+        a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
+        _check(lib().vdb_filter_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
+        return {"mark_ms": a.value, "scan_ms": b.value, "merge_ms": c.value, "pairs_scanned": r.value}
 
     def search_device(self, q_ptr: int, n: int, nprobe: int, k: int, d_ptr: int, i_ptr: int,
                       stream: int | None = None):

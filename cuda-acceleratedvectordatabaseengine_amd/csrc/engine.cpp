@@ -4,6 +4,7 @@
 
 #include <cmath>
 
+#include "filter.hpp"
 #include "remove.hpp"
 #include "remove_plan.hpp"
 
@@ -409,6 +410,27 @@ int vdb_ivf_search(vdb_ivf* h, const float* q, uint32_t n, uint32_t nprobe, uint
             h->search_host(q, n, nprobe, k, dist, ids, nullptr);
         }
     });
+}
+
+int vdb_ivf_search_filtered(vdb_ivf* h, const float* q, uint32_t n, uint32_t nprobe, uint32_t k,
+                            const uint64_t* filter_ids, uint64_t n_filter, int mode, float* dist, uint64_t* ids) {
+    return guarded([&] {
+        require(h && ((q && dist && ids) || n == 0 || k == 0) && (filter_ids || n_filter == 0), "null argument");
+        require(mode == VDB_FILTER_EXCLUDE || mode == VDB_FILTER_INCLUDE, "invalid filter mode");
+        require(n_filter < (1ull << 31), "more than 2^31 - 1 ids in one filter", VDB_ERR_UNSUPPORTED);
+        const std::vector<uint64_t> sorted = remove_sorted_ids(filter_ids, n_filter);  // (before the lock)
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        search_filtered(*h, q, n, nprobe, k, sorted, mode == VDB_FILTER_INCLUDE, dist, ids);
+    });
+}
+
+int vdb_filter_last_timing(double* mark_ms, double* scan_ms, double* merge_ms, uint64_t* pairs_scanned) {
+    if (mark_ms) *mark_ms = g_filter_timing.mark_ms;
+    if (scan_ms) *scan_ms = g_filter_timing.scan_ms;
+    if (merge_ms) *merge_ms = g_filter_timing.merge_ms;
+    if (pairs_scanned) *pairs_scanned = g_filter_timing.pairs_scanned;
+    return VDB_OK;
 }
 
 int vdb_ivf_search_device(vdb_ivf* h, const float* d_q, uint32_t n, uint32_t nprobe, uint32_t k, float* d_dist,

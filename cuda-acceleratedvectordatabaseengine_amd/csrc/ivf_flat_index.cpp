@@ -59,6 +59,14 @@ void IVFFlatIndex::search(const float* queries, uint32_t n_queries, const Search
     ok(vdb_ivf_search(h_, queries, n_queries, params.nprobe, params.k, distances, indices), "search");
 }
 
+void IVFFlatIndex::search_filtered(const float* queries, uint32_t n_queries, const SearchParams& params,
+                                   const uint64_t* ids, uint64_t n_ids, bool include, float* distances,
+                                   uint64_t* indices) {
+    ok(vdb_ivf_search_filtered(h_, queries, n_queries, params.nprobe, params.k, ids, n_ids,
+                               include ? VDB_FILTER_INCLUDE : VDB_FILTER_EXCLUDE, distances, indices),
+       "search_filtered");
+}
+
 void IVFFlatIndex::search_batch(const std::vector<float*>& queries, const std::vector<SearchParams>& params,
                                 std::vector<float*>& distances, std::vector<uint64_t*>& indices) {
     if (params.size() != queries.size() || distances.size() != queries.size() || indices.size() != queries.size())

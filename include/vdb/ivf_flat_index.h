@@ -54,6 +54,11 @@ public:
     uint64_t remove(const uint64_t* ids, uint64_t n_ids);
     void search(const float* queries, uint32_t n_queries, const SearchParams& params, float* distances,
                 uint64_t* indices);
+    // Not in the reference: search over the stored rows the id filter allows
+    // (vdb_ivf_search_filtered). include: only rows whose id is listed; else every row whose
+    // id is not. The result is search()'s on an index holding only the allowed rows.
+    void search_filtered(const float* queries, uint32_t n_queries, const SearchParams& params, const uint64_t* ids,
+                         uint64_t n_ids, bool include, float* distances, uint64_t* indices);
     // Declared but never defined in the reference: here request i searches the single
     // query queries[i] with params[i] into distances[i] / indices[i] (params[i].k slots).
     void search_batch(const std::vector<float*>& queries, const std::vector<SearchParams>& params,

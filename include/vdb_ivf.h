@@ -159,6 +159,39 @@ int vdb_ivf_remove_ids(vdb_ivf* index, const uint64_t* ids, uint64_t n, uint64_t
  * step: the mark kernel and the compact kernel (HIP events), the host plan between them, and
  * the rows the compact pass moved. Any pointer may be NULL. */
 int vdb_remove_last_timing(double* mark_ms, double* plan_ms, double* compact_ms, uint64_t* rows_kept);
+/* Filtered search: vdb_ivf_search over the stored rows an id filter allows. filter_ids[0..
+ * n_filter) is a host array in any order; repeats and ids that are not stored are ignored.
+ * VDB_FILTER_EXCLUDE: a stored row is allowed unless its id is listed (tombstones: n_filter
+ * == 0 is valid and equals vdb_ivf_search). VDB_FILTER_INCLUDE: a stored row is allowed only
+ * if its id is listed (pre-filtering; nothing allowed: every slot unfilled). Pad slots are
+ * never allowed, whatever filter_ids holds. Host buffers in and out, as for vdb_ivf_search.
+ * The result is, bit for bit (ids and distance bits), the one vdb_ivf_search(n, nprobe, k)
+ * gives on a handle with the same centroids, metric and stale_slots setting that stores only
+ * the allowed rows in their original order: probe selection unchanged (centroids only, nprobe
+ * clamped to nlist), per list the top-k by (distance, id), the unique-id merge over the slots,
+ * (FLT_MAX, UINT64_MAX) in unfilled slots; with stale_slots = 1 a slot whose list has no
+ * allowed row keeps the content of the latest earlier query of the call whose probe at that
+ * slot had one. Results never depend on the `batch` option. Cosine is served (every distance
+ * 0.0f, ties by id).
+ * No counterpart in the reference. Nothing moves and nothing is rebuilt: the allow masks are
+ * taken per call from the ids, a masked exact scan computes the allowed rows' distances only
+ * (the screen is not used: its shadow and thresholds describe whole lists), and the handle is
+ * left exactly as found. The call holds the handle's lock and has finished its device work
+ * when it returns.
+ * Limits of this version (the handle is untouched by a refusal): k > 64 and n_filter >= 2^31
+ * give VDB_ERR_UNSUPPORTED; an invalid mode or a null buffer VDB_ERR_INVALID_ARGUMENT; a handle
+ * in the list-cache tier (option list_cache_bytes, or max_gpu_memory exceeded), a file-home
+ * handle (vdb_ivf_open_lists), a sharded handle (world > 1) and a group handle give
+ * VDB_ERR_UNSUPPORTED. Not offered yet: a prepared, reusable filter object, a device-pointer
+ * variant, the gRPC service, coalescing of concurrent filtered calls. */
+enum { VDB_FILTER_EXCLUDE = 0, VDB_FILTER_INCLUDE = 1 };
+int vdb_ivf_search_filtered(vdb_ivf* index, const float* queries, uint32_t n, uint32_t nprobe, uint32_t k,
+                            const uint64_t* filter_ids, uint64_t n_filter, int mode,
+                            float* distances, uint64_t* ids);
+/* Diagnostics: the calling thread's latest vdb_ivf_search_filtered, by step (HIP events: the
+ * mark and count kernels; the masked scan and the merge, each summed over the call's
+ * batches), and the (query, row) distances computed. Any pointer may be NULL. */
+int vdb_filter_last_timing(double* mark_ms, double* scan_ms, double* merge_ms, uint64_t* pairs_scanned);
 /* Persist / restore centroids and lists (IVFFlatIndex::save/load, engine/ivf_flat_index.h:66-67,
  * declared but never defined in the reference; this engine's own file format). */
 int vdb_ivf_save(vdb_ivf* index, const char* path);
