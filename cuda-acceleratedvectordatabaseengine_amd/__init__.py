@@ -121,6 +121,15 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_search_filtered": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, u64, ctypes.c_int, vp, vp]),
         "vdb_filter_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_range_search": (ctypes.c_int, [vp, vp, u32, u32, ctypes.c_float, u64, ctypes.POINTER(vp)]),
+        "vdb_range_result_n": (u32, [vp]),
+        "vdb_range_result_lims": (vp, [vp]),
+        "vdb_range_result_distances": (vp, [vp]),
+        "vdb_range_result_ids": (vp, [vp]),
+        "vdb_range_result_free": (None, [vp]),
+        "vdb_range_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                                 ctypes.POINTER(ctypes.c_uint32)]),
         "vdb_ivf_search_device": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "vdb_ivf_set_shard": (ctypes.c_int, [vp, u32, u32]),
         "vdb_ivf_plan_shard": (ctypes.c_int, [vp, u32, u32, vp]),
@@ -405,6 +414,40 @@ class IVFFlatIndex:
         a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
         _check(lib().vdb_filter_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
         return {"mark_ms": a.value, "scan_ms": b.value, "merge_ms": c.value, "pairs_scanned": r.value}
+
+    def range_search(self, queries: np.ndarray, radius: float, *, nprobe: int = 10, reserve: int = 0):
+        """Every stored row within `radius` of each query among the lists it probes
+        (vdb_ivf_range_search; not in the reference). Returns (lims, distances, ids): query i
+        owns entries [lims[i], lims[i + 1]), ascending by (distance, id) — search's entries for
+        that query alone with d <= radius, however many there are. reserve: entries of the
+        device hit buffer a batch starts with (0: automatic)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
+        n = q.shape[0]
+        L = lib()
+        r = ctypes.c_void_p()
+        _check(L.vdb_ivf_range_search(self._h, _ptr(q), n, nprobe, float(radius), reserve, ctypes.byref(r)))
+        try:
+            lims = np.ctypeslib.as_array(ctypes.cast(L.vdb_range_result_lims(r), ctypes.POINTER(ctypes.c_uint64)),
+                                         shape=(n + 1,)).copy()
+            total = int(lims[n])
+            if total:
+                D = np.ctypeslib.as_array(ctypes.cast(L.vdb_range_result_distances(r), ctypes.POINTER(ctypes.c_float)),
+                                          shape=(total,)).copy()
+                I = np.ctypeslib.as_array(ctypes.cast(L.vdb_range_result_ids(r), ctypes.POINTER(ctypes.c_uint64)),
+                                          shape=(total,)).copy()
+            else:
+                D, I = np.empty(0, dtype=np.float32), np.empty(0, dtype=np.uint64)
+        finally:
+            L.vdb_range_result_free(r)
+        return lims, D, I
+
+    def range_last_timing(self) -> dict:
+        """The calling thread's latest range_search by step (vdb_range_last_timing)."""
+        a, b = ctypes.c_double(0), ctypes.c_double(0)
+        p, h, r = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+        _check(lib().vdb_range_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(p), ctypes.byref(h),
+                                           ctypes.byref(r)))
+        return {"scan_ms": a.value, "order_ms": b.value, "pairs_scanned": p.value, "hits": h.value, "reruns": r.value}
 
     def search_device(self, q_ptr: int, n: int, nprobe: int, k: int, d_ptr: int, i_ptr: int,
                       stream: int | None = None):

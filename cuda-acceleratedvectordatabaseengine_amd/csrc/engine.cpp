@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "filter.hpp"
+#include "range.hpp"
 #include "remove.hpp"
 #include "remove_plan.hpp"
 
@@ -430,6 +431,32 @@ int vdb_filter_last_timing(double* mark_ms, double* scan_ms, double* merge_ms, u
     if (scan_ms) *scan_ms = g_filter_timing.scan_ms;
     if (merge_ms) *merge_ms = g_filter_timing.merge_ms;
     if (pairs_scanned) *pairs_scanned = g_filter_timing.pairs_scanned;
+    return VDB_OK;
+}
+
+int vdb_ivf_range_search(vdb_ivf* h, const float* q, uint32_t n, uint32_t nprobe, float radius, uint64_t reserve,
+                         vdb_range_result** out) {
+    return guarded([&] {
+        require(h && (q || n == 0) && out, "null argument");
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        *out = range_search(*h, q, n, nprobe, radius, reserve).release();
+    });
+}
+
+uint32_t vdb_range_result_n(const vdb_range_result* r) { return r ? r->n : 0; }
+const uint64_t* vdb_range_result_lims(const vdb_range_result* r) { return r ? r->lims.data() : nullptr; }
+const float* vdb_range_result_distances(const vdb_range_result* r) { return r ? r->distances.data() : nullptr; }
+const uint64_t* vdb_range_result_ids(const vdb_range_result* r) { return r ? r->ids.data() : nullptr; }
+void vdb_range_result_free(vdb_range_result* r) { delete r; }
+
+int vdb_range_last_timing(double* scan_ms, double* order_ms, uint64_t* pairs_scanned, uint64_t* hits,
+                          uint32_t* reruns) {
+    if (scan_ms) *scan_ms = g_range_timing.scan_ms;
+    if (order_ms) *order_ms = g_range_timing.order_ms;
+    if (pairs_scanned) *pairs_scanned = g_range_timing.pairs_scanned;
+    if (hits) *hits = g_range_timing.hits;
+    if (reruns) *reruns = g_range_timing.reruns;
     return VDB_OK;
 }
 

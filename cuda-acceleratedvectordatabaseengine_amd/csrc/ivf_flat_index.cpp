@@ -67,6 +67,22 @@ void IVFFlatIndex::search_filtered(const float* queries, uint32_t n_queries, con
        "search_filtered");
 }
 
+void IVFFlatIndex::range_search(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
+                                std::vector<uint64_t>& lims, std::vector<float>& distances,
+                                std::vector<uint64_t>& indices) {
+    vdb_range_result* r = nullptr;
+    ok(vdb_ivf_range_search(h_, queries, n_queries, nprobe, radius, 0, &r), "range_search");
+    struct Free {
+        vdb_range_result* r;
+        ~Free() { vdb_range_result_free(r); }
+    } guard{r};
+    const uint64_t* l = vdb_range_result_lims(r);
+    const uint64_t total = l[n_queries];
+    lims.assign(l, l + n_queries + 1);
+    distances.assign(vdb_range_result_distances(r), vdb_range_result_distances(r) + total);
+    indices.assign(vdb_range_result_ids(r), vdb_range_result_ids(r) + total);
+}
+
 void IVFFlatIndex::search_batch(const std::vector<float*>& queries, const std::vector<SearchParams>& params,
                                 std::vector<float*>& distances, std::vector<uint64_t*>& indices) {
     if (params.size() != queries.size() || distances.size() != queries.size() || indices.size() != queries.size())

@@ -1,0 +1,231 @@
+// range.cpp — vdb_ivf_range_search on one handle: every stored row within a radius of each
+// query, through a thresholded exact scan.
+//
+// "The result of a range search" is, for each query on its own, the result vdb_ivf_search
+// gives that single query with the same nprobe and a k no smaller than the rows it probes,
+// cut to the entries with id != UINT64_MAX and d <= radius: the reference's sequential fp32
+// distances bit for bit, an id stored more than once among the probed lists once at its
+// smallest distance, ascending by (distance, id). A query answered alone has no stale slot, so
+// the result depends on neither stale_slots nor batch.
+//
+// Per batch: the handle's own coarse step, the pairs grouped by list (launch_range_group: eight
+// queries share one read of a list), the thresholded scan (ivf_range_scan: hits appended
+// to a buffer through one global cursor) and the ordering on the device (three stable radix
+// sorts around range_dedup, then range_finish). The size of a batch's result is known only
+// after its scan: a batch whose hits exceed the buffer is scanned once more with a buffer of
+// the size the cursor counted. The lists are read in the fp32 layout the handle holds at that
+// moment: the interleaved arena, or the screen's row-major copy while the arena is dropped.
+// Exact scan only.
+//
+// A free function over vdb_ivf's public members, as filter.cpp is and for the same reason. It
+// calls nothing that changes the handle: no screen_update, screen_release, ensure_arena or
+// upload_directory; the workspace is the call's own.
+#include "range.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+#include "filter_kernels.hpp"
+#include "range_kernels.hpp"
+
+namespace vdbe {
+
+thread_local RangeTiming g_range_timing;
+
+namespace {
+
+struct Events {
+    hipEvent_t e[4] = {};  // scan begin, scan end, order begin, order end
+    Events() {
+        for (auto& x : e) HIPCHECK(hipEventCreate(&x));
+    }
+    ~Events() {
+        for (auto& x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    double ms(int a, int b) {
+        float t = 0.f;
+        HIPCHECK(hipEventElapsedTime(&t, e[a], e[b]));
+        return t;
+    }
+};
+
+// The stream is idle before the call's buffers go and before the caller releases the mutex,
+// on every way out.
+struct StreamFence {
+    hipStream_t s;
+    ~StreamFence() { (void)hipStreamSynchronize(s); }
+};
+
+// The device buffers that hold and order a batch's hits: one allocation, cut into the four
+// key / id arrays, the two permutations and the sorts' scratch.
+struct HitBufs {
+    DevBuf<unsigned char> slab;
+    uint64_t *key_a = nullptr, *id_a = nullptr, *key_b = nullptr, *id_b = nullptr;
+    uint32_t *perm_a = nullptr, *perm_b = nullptr;
+    void* temp = nullptr;
+    uint64_t cap = 0;
+    size_t temp_bytes = 0;
+    void ensure(uint64_t entries, uint32_t B) {
+        if (entries <= cap) return;
+        HIPCHECK(vdbk::range_order_temp_bytes(entries, B, temp_bytes));
+        const size_t e8 = (entries * 8 + 255) / 256 * 256, e4 = (entries * 4 + 255) / 256 * 256;
+        unsigned char* p = slab.ensure(4 * e8 + 2 * e4 + temp_bytes);
+        key_a = (uint64_t*)p;
+        id_a = (uint64_t*)(p + e8);
+        key_b = (uint64_t*)(p + 2 * e8);
+        id_b = (uint64_t*)(p + 3 * e8);
+        perm_a = (uint32_t*)(p + 4 * e8);
+        perm_b = (uint32_t*)(p + 4 * e8 + e4);
+        temp = p + 4 * e8 + 2 * e4;
+        cap = entries;
+    }
+};
+
+}  // namespace
+
+std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe,
+                                               float radius, uint64_t reserve) {
+    require(!std::isnan(radius), "the radius is NaN");
+    require(!h.is_group(), "range_search is not available on a group handle", VDB_ERR_UNSUPPORTED);
+    require(h.world == 1 && h.comm_world == 1,
+            "range_search is not available on a sharded handle (set_shard / plan_shard / a shard file / "
+            "attach_comm with world > 1)",
+            VDB_ERR_UNSUPPORTED);
+    require(!h.file_home(), "range_search is not available while the lists are served from a file (vdb_ivf_open_lists)",
+            VDB_ERR_UNSUPPORTED);
+    require(!h.tiered() && !h.arena.host,
+            "range_search is not available in the list-cache tier (list_cache_bytes, or max_gpu_memory exceeded)",
+            VDB_ERR_UNSUPPORTED);
+    g_range_timing = RangeTiming{};
+    auto res = std::make_unique<vdb_range_result>();
+    res->n = n;
+    res->lims.assign((size_t)n + 1, 0);
+    if (n == 0) return res;
+    const uint32_t P = std::min(nprobe, h.nlist);
+    require(P <= (uint32_t)vdbk::kMaxK, "nprobe above 1024 is not supported", VDB_ERR_UNSUPPORTED);
+    if (P == 0 || h.arena_blocks == 0 || h.total == 0) return res;
+    const float4* lists = h.arena_dropped ? (const float4*)h.screen_rows.p : h.arena.p;
+    require(lists != nullptr && h.arena_ids.p != nullptr, "the handle holds no fp32 copy of its lists", VDB_ERR_STATE);
+
+    hipStream_t s = h.stream;
+    DevBuf<uint32_t> d_cursor, d_pair_start, d_item_start, d_inv, d_start;
+    DevBuf<unsigned long long> d_ctrl;
+    DevBuf<float> d_q;
+    HitBufs hit;
+    vdb_ivf::SearchSlot w;  // the call's own workspace, not one of the ring's
+    Events ev;
+    StreamFence fence{s};  // (declared last: the stream is idle before anything above goes)
+
+    HIPCHECK(hipMemcpyAsync(d_q.ensure((size_t)n * h.dim), queries, (size_t)n * h.dim * 4, hipMemcpyHostToDevice, s));
+
+    // a list longer than kFilterSegBlocks blocks is cut into segments (the longest list's: the cap)
+    uint64_t longest = 0;
+    for (uint32_t l = 0; l < h.nlist; ++l)
+        if (h.owned[l]) longest = std::max(longest, cdiv(h.count[l], 64));
+    const uint32_t segs = vdbk::filter_segs((uint32_t)longest, vdbk::kFilterMaxSegs);
+
+    const uint32_t bmax = std::min(h.batch_cap(P, 1), n);
+    h.ensure_workspace(w, bmax, P, 1);
+    d_cursor.ensure(h.nlist);
+    d_pair_start.ensure((size_t)h.nlist + 1);
+    d_item_start.ensure((size_t)h.nlist + 1);
+    d_inv.ensure((size_t)bmax * P);
+    d_start.ensure((size_t)bmax + 1);
+    d_ctrl.ensure(vdbk::kRangeCtrlWords);
+    hit.ensure(std::min<uint64_t>(reserve ? reserve : kRangeAutoReserve, (1ull << 31) - 1), bmax);
+    std::vector<uint32_t> start((size_t)bmax + 1);
+
+    for (uint32_t b0 = 0, B = bmax; b0 < n; b0 += B, B = std::min(B, n - b0)) {
+        // 1. the handle's own coarse step: padded queries (w.q) and probes (w.probes)
+        h.coarse_batch(w, d_q.p + (size_t)b0 * h.dim, B, P, s);
+        HIPCHECK(hipGetLastError());
+        // 2. the pairs grouped by list, one item per (list segment, 8 queries); empty lists get none
+        HIPCHECK(hipEventRecord(ev.e[0], s));
+        vdbk::launch_range_group(w.probes.p, B * P, h.d_count_local.p, h.nlist, segs, d_cursor.p, d_pair_start.p,
+                                 d_item_start.p, d_inv.p, s);
+        HIPCHECK(hipGetLastError());
+        // 3. the thresholded scan, once more if the hits did not fit
+        unsigned long long ctrl[vdbk::kRangeCtrlWords] = {};
+        for (int pass = 0;; ++pass) {
+            vdbk::RangeScanArgs a;
+            a.lists = lists;
+            a.ids = h.arena_ids.p;
+            a.block_off = h.d_block_off.p;
+            a.count = h.d_count_local.p;
+            a.q = w.q;
+            a.inv = d_inv.p;
+            a.pair_start = d_pair_start.p;
+            a.item_start = d_item_start.p;
+            a.nlist = h.nlist;
+            a.B = B;
+            a.P = P;
+            a.d4 = h.d4;
+            a.segs = segs;
+            a.rows = h.arena_dropped ? 1 : 0;
+            a.radius = radius;
+            a.cap = hit.cap;
+            a.hit_key = hit.key_a;
+            a.hit_id = hit.id_a;
+            a.ctrl = d_ctrl.p;
+            require(vdbk::range_scan_serves(a), "range_search: the row padding does not fit the scan's LDS tile",
+                    VDB_ERR_STATE);
+            if (pass) HIPCHECK(hipEventRecord(ev.e[0], s));
+            HIPCHECK(hipMemsetAsync(d_ctrl.p, 0, sizeof(ctrl), s));
+            vdbk::launch_range_scan(h.metric, a, s);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipEventRecord(ev.e[1], s));
+            HIPCHECK(hipMemcpyAsync(ctrl, d_ctrl.p, sizeof(ctrl), hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipStreamSynchronize(s));
+            g_range_timing.scan_ms += ev.ms(0, 1);
+            g_range_timing.pairs_scanned += ctrl[vdbk::kRangePairs];
+            require(!(ctrl[vdbk::kRangeStatus] & vdbk::kRangeUnserved),
+                    "range_search: the scan kernel refused the launch's shape", VDB_ERR_STATE);
+            const unsigned long long m = ctrl[vdbk::kRangeCursor];
+            require(m < (1ull << 31),
+                    "range_search: more than 2^31 - 1 hits in one batch (lower the `batch` option or the radius)",
+                    VDB_ERR_UNSUPPORTED);
+            if (m <= hit.cap) break;
+            require(pass == 0, "range_search: the hit count changed between two scans of a batch", VDB_ERR_STATE);
+            hit.ensure(m, bmax);  // (the stream is idle)
+            ++g_range_timing.reruns;
+        }
+        // 4. order and de-duplicate on the device, then the batch's part of the result
+        const uint64_t m = ctrl[vdbk::kRangeCursor];
+        const uint64_t at = res->ids.size();
+        uint64_t kept = 0;
+        if (m) {
+            vdbk::RangeOrderBufs o;
+            o.key_a = hit.key_a;
+            o.id_a = hit.id_a;
+            o.key_b = hit.key_b;
+            o.id_b = hit.id_b;
+            o.perm_a = hit.perm_a;
+            o.perm_b = hit.perm_b;
+            o.temp = hit.temp;
+            o.temp_bytes = hit.temp_bytes;
+            o.start = d_start.p;
+            HIPCHECK(hipEventRecord(ev.e[2], s));
+            HIPCHECK(vdbk::launch_range_order(o, m, B, s));
+            HIPCHECK(hipEventRecord(ev.e[3], s));
+            HIPCHECK(hipMemcpyAsync(start.data(), d_start.p, ((size_t)B + 1) * 4, hipMemcpyDeviceToHost, s));
+            HIPCHECK(hipStreamSynchronize(s));
+            g_range_timing.order_ms += ev.ms(2, 3);
+            kept = start[B];
+            res->ids.resize(at + kept);
+            res->distances.resize(at + kept);
+            if (kept) {
+                HIPCHECK(hipMemcpyAsync(res->ids.data() + at, o.key_b, kept * 8, hipMemcpyDeviceToHost, s));
+                HIPCHECK(hipMemcpyAsync(res->distances.data() + at, o.perm_a, kept * 4, hipMemcpyDeviceToHost, s));
+                HIPCHECK(hipStreamSynchronize(s));
+            }
+        } else {
+            std::fill(start.begin(), start.end(), 0u);
+        }
+        for (uint32_t i = 0; i < B; ++i) res->lims[(size_t)b0 + i + 1] = at + start[i + 1];
+    }
+    g_range_timing.hits = res->ids.size();
+    return res;
+}
+
+}  // namespace vdbe

@@ -1,0 +1,41 @@
+// range.hpp — vdb_ivf_range_search on one handle (range.cpp), for the C ABI entries
+// (engine.cpp).
+#pragma once
+
+#include <memory>
+#include <vector>
+
+#include "engine.hpp"
+
+// What vdb_ivf_range_search hands out: host memory only, nothing of the handle.
+struct vdb_range_result {
+    uint32_t n = 0;
+    std::vector<uint64_t> lims;  // n + 1
+    std::vector<float> distances;
+    std::vector<uint64_t> ids;
+};
+
+namespace vdbe {
+
+constexpr uint64_t kRangeAutoReserve = 1ull << 18;  // reserve == 0: entries of the hit buffer a batch starts with
+
+// The calling thread's latest range_search (vdb_range_last_timing).
+struct RangeTiming {
+    double scan_ms = 0.0;        // pair grouping + ivf_range_scan, summed over the call's batches, re-runs included
+    double order_ms = 0.0;       // the sorts, range_dedup and range_finish, summed over the call's batches
+    uint64_t pairs_scanned = 0;  // (query, row) distances computed, re-runs included
+    uint64_t hits = 0;           // entries returned
+    uint32_t reruns = 0;         // batches scanned again with a larger hit buffer
+};
+extern thread_local RangeTiming g_range_timing;
+
+// Caller holds h.mu and has made h's device current. For each of the n host queries on its
+// own: every entry (d, id) of the result vdb_ivf_search gives that query with the same nprobe
+// and a k no smaller than the rows it probes, keeping id != UINT64_MAX and d <= radius, in that
+// result's order. Reads the handle only, and has synchronised h.stream when it returns or
+// throws. Refuses what it does not serve (a NaN radius, a group, a shard, a file home, the
+// list-cache tier) before any device work.
+std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe,
+                                               float radius, uint64_t reserve);
+
+}  // namespace vdbe

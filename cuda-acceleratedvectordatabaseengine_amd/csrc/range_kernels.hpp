@@ -1,0 +1,74 @@
+// range_kernels.hpp — launchers of the kernels behind vdb_ivf_range_search
+// (range_kernels.hip, gfx950, wave64).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace vdbk {
+
+constexpr uint32_t kRangeGroup = 8;   // queries that probe the same list share one read of it
+constexpr uint32_t kRangeChunk4 = 8;  // row-major layout: float4 of a row staged through LDS per step
+
+// The device words a scan reports through (cleared by the caller before every scan).
+enum { kRangeCursor = 0, kRangeStatus = 1, kRangePairs = 2, kRangeNext = 3, kRangeCtrlWords = 4 };  // (kRangeNext: the scan's item counter)
+constexpr unsigned long long kRangeUnserved = 1;  // status bit: a device guard refused the launch's shape
+
+// The batch's (query, probe) pairs grouped by probed list, pairs of an empty list left out:
+// inv[pair_start[l] .. pair_start[l + 1]) are the pairs (q * P + p) that probe list l, in no
+// particular order. item_start[l] is the first scan item of list l: a list has
+// cdiv(pairs, kRangeGroup) x filter_segs(blocks, segs) items; item_start[nlist] is their
+// number. cursor is scratch ([nlist]). (launch_filter_invert with a group of kRangeGroup.)
+void launch_range_group(const uint32_t* probes, uint32_t BP, const uint32_t* count, uint32_t nlist, uint32_t segs,
+                        uint32_t* cursor, uint32_t* pair_start, uint32_t* item_start, uint32_t* inv, hipStream_t s);
+
+struct RangeScanArgs {
+    const float4* lists = nullptr;  // rows == 0: [block][d4][64] float4; rows != 0: [slot][d4] float4
+    const uint64_t* ids = nullptr;  // [block][64]
+    const uint64_t* block_off = nullptr;  // per list
+    const uint32_t* count = nullptr;      // per list
+    const float* q = nullptr;             // the batch's padded queries [B][d4 * 4]
+    const uint32_t* inv = nullptr;        // launch_range_group
+    const uint32_t* pair_start = nullptr;
+    const uint32_t* item_start = nullptr;
+    uint32_t nlist = 0, B = 0, P = 0, d4 = 0;
+    uint32_t segs = 1;  // the call's segment cap (1 .. kFilterMaxSegs)
+    int rows = 0;
+    float radius = 0.0f;
+    uint64_t cap = 0;             // entries hit_key / hit_id hold
+    uint64_t* hit_key = nullptr;  // (batch query << 32) | ord_enc(distance)
+    uint64_t* hit_id = nullptr;
+    unsigned long long* ctrl = nullptr;  // [kRangeCtrlWords]
+};
+// True if the scan kernel serves this shape (its fixed-size LDS tile: whole chunks of
+// kRangeChunk4 float4 per row). The kernel checks the same and sets kRangeUnserved.
+inline bool range_scan_serves(const RangeScanArgs& a) { return a.d4 > 0 && a.d4 % kRangeChunk4 == 0; }
+
+// Persistent workgroups over the items of launch_range_group: one segment of one list against
+// up to kRangeGroup of the queries that probe it. Every slot below its block's valid count
+// whose exact distance d satisfies d <= radius is appended at ctrl[kRangeCursor] (one atomic
+// per wave and query); past `cap` nothing is written and the cursor keeps counting.
+// ctrl[kRangePairs] grows by the (query, row) distances computed.
+void launch_range_scan(int metric, const RangeScanArgs& a, hipStream_t s);
+
+// The buffers that order m appended hits (each of at least m entries).
+struct RangeOrderBufs {
+    uint64_t* key_a = nullptr;  // in: the scan's hit_key
+    uint64_t* id_a = nullptr;   // in: the scan's hit_id
+    uint64_t* key_b = nullptr;  // out: the ordered ids
+    uint64_t* id_b = nullptr;
+    uint32_t* perm_a = nullptr;  // out: the ordered distances (as float)
+    uint32_t* perm_b = nullptr;
+    void* temp = nullptr;
+    size_t temp_bytes = 0;
+    uint32_t* start = nullptr;  // out [B + 1]: query i of the batch owns [start[i], start[i + 1])
+};
+// Bytes of `temp` launch_range_order needs for m hits of a batch of B queries.
+hipError_t range_order_temp_bytes(uint64_t m, uint32_t B, size_t& bytes);
+// m >= 1 hits in arbitrary order into per query ascending (distance, id) (-0.0f ties +0.0f),
+// an id stored more than once for a query kept once at its smallest distance. start[B] is the
+// number of entries left.
+hipError_t launch_range_order(const RangeOrderBufs& b, uint64_t m, uint32_t B, hipStream_t s);
+
+}  // namespace vdbk

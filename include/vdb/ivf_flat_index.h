@@ -59,6 +59,12 @@ public:
     // id is not. The result is search()'s on an index holding only the allowed rows.
     void search_filtered(const float* queries, uint32_t n_queries, const SearchParams& params, const uint64_t* ids,
                          uint64_t n_ids, bool include, float* distances, uint64_t* indices);
+    // Not in the reference: every stored row within `radius` of each query among the lists it
+    // probes (vdb_ivf_range_search). Query i owns entries [lims[i], lims[i + 1]) of distances
+    // and indices, ascending by (distance, id): search()'s entries for that query alone with
+    // d <= radius, however many there are.
+    void range_search(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
+                      std::vector<uint64_t>& lims, std::vector<float>& distances, std::vector<uint64_t>& indices);
     // Declared but never defined in the reference: here request i searches the single
     // query queries[i] with params[i] into distances[i] / indices[i] (params[i].k slots).
     void search_batch(const std::vector<float*>& queries, const std::vector<SearchParams>& params,

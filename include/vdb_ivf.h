@@ -192,6 +192,50 @@ int vdb_ivf_search_filtered(vdb_ivf* index, const float* queries, uint32_t n, ui
  * mark and count kernels; the masked scan and the merge, each summed over the call's
  * batches), and the (query, row) distances computed. Any pointer may be NULL. */
 int vdb_filter_last_timing(double* mark_ms, double* scan_ms, double* merge_ms, uint64_t* pairs_scanned);
+/* Range search: every stored row within `radius` of each query (FAISS: range_search). For each
+ * of the n host queries on its own, the result holds every entry (d, id) of the result
+ * vdb_ivf_search gives that single query with the same nprobe and a k no smaller than the rows
+ * it probes, keeping the entries with id != UINT64_MAX and d <= radius, in that result's order:
+ * probe selection unchanged (centroids only, nprobe clamped to nlist); distances the
+ * reference's sequential fp32 sums, bit for bit (L2 squared, inner product negated, Cosine
+ * 0.0f for every row); the comparison the fp32 d <= radius, inclusive (a NaN distance is never
+ * returned; +inf and FLT_MAX return every probed row); an id stored more than once among the
+ * probed lists once, at its smallest distance; a query's entries ascending by (distance, id),
+ * -0.0f and +0.0f equal and tied by id, the returned bits the computed ones. The result depends
+ * on neither stale_slots nor batch; pad slots are never returned.
+ * The size of the answer is not known before the call, so the library owns it: *out (written
+ * only on success) holds host memory alone, nothing of the handle, outlives it, and is released
+ * with vdb_range_result_free (NULL is fine). Query i owns entries [lims[i], lims[i + 1]) of
+ * distances and ids; lims has n + 1 entries. n == 0 gives lims = {0}; an empty index or nprobe
+ * == 0 all-zero lims.
+ * reserve is the capacity, in entries, of the device hit buffer a batch starts with (about 56
+ * bytes of device workspace per entry); 0 chooses 262,144. A batch that finds more hits than the
+ * buffer holds is scanned once more with a buffer of the size it counted (at most one re-run
+ * per batch; results are identical).
+ * Nothing moves and nothing is rebuilt: a thresholded exact scan appends the hits, three stable
+ * device sorts order and de-duplicate them, and the handle is left exactly as found (the screen
+ * is not used). The call holds the handle's lock and has finished its device work when it
+ * returns.
+ * Limits of this version (the handle is untouched by a refusal): a null handle, queries or out
+ * and a NaN radius give VDB_ERR_INVALID_ARGUMENT; a handle in the list-cache tier, a file-home
+ * handle, a sharded handle and a group handle give VDB_ERR_UNSUPPORTED, as does a batch with
+ * more than 2^31 - 1 hits (lower the `batch` option). Not offered yet: a screened range scan,
+ * per-query radii, a device-pointer variant, a filter combined with a radius, the gRPC service,
+ * coalescing of concurrent range calls. */
+typedef struct vdb_range_result vdb_range_result;
+int vdb_ivf_range_search(vdb_ivf* index, const float* queries, uint32_t n, uint32_t nprobe, float radius,
+                         uint64_t reserve, vdb_range_result** out);
+uint32_t vdb_range_result_n(const vdb_range_result* r);
+const uint64_t* vdb_range_result_lims(const vdb_range_result* r);      /* n + 1 entries; query i owns [lims[i], lims[i+1]) */
+const float* vdb_range_result_distances(const vdb_range_result* r);    /* lims[n] entries */
+const uint64_t* vdb_range_result_ids(const vdb_range_result* r);
+void vdb_range_result_free(vdb_range_result* r);                       /* NULL is fine */
+/* Diagnostics: the calling thread's latest vdb_ivf_range_search (HIP events summed over the
+ * call's batches, re-runs included): the scan with the pair grouping, the ordering (sorts,
+ * de-duplication, per-query counts), the (query, row) distances computed, the entries returned
+ * and the batches run again. Any pointer may be NULL; a thread without a call reads zeros. */
+int vdb_range_last_timing(double* scan_ms, double* order_ms, uint64_t* pairs_scanned, uint64_t* hits,
+                          uint32_t* reruns);
 /* Persist / restore centroids and lists (IVFFlatIndex::save/load, engine/ivf_flat_index.h:66-67,
  * declared but never defined in the reference; this engine's own file format). */
 int vdb_ivf_save(vdb_ivf* index, const char* path);

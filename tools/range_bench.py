@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""Measure vdb_ivf_range_search (DESIGN.md "Range search").
+
+Builds an index of device-generated N(0,1) rows (vdb_gen_normal_device) and times, on the one
+handle and for one batch of `--queries` host queries per call (wall time of the host call, PCIe
+and the copy of the result included):
+  plain   vdb_ivf_search with screen = 0 and k = 10 (the plain exact scan: the yardstick, same
+          run, same handle) and with screen = 1
+  range   vdb_ivf_range_search at four radii taken from a k = 10 search of the same queries: one
+          below every distance (no hit), the median 10th distance, the radius that returns about
+          1 % of the probed rows, and +inf (every probed row), with its scan / order split (HIP
+          events), the (query, row) distances computed, the entries returned, the batches run
+          again, and the scan's read rate on 4 * dp * pairs_scanned / group bytes (group: the
+          queries that share one read of a list, from the probes recomputed on the host)
+The range calls run in both list layouts a handle can hold: the interleaved arena (screen = 0)
+and the screen's row-major copy (screen = 1, after a plain search). Each figure is the median of
+`--repeats` calls after one warm-up call, with min and max. Prints one JSON line per leg.
+
+  python tools/range_bench.py [--n 1000000 --dim 768 --nlist 256 --nprobe 16 --queries 64 --repeats 7]
+"""
+import argparse
+import importlib.util
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG_DIR = os.path.join(ROOT, "cuda-acceleratedvectordatabaseengine_amd")
+GROUP = 8  # kRangeGroup: queries of a list that share one read of it
+
+
+def load_vdb():
+    spec = importlib.util.spec_from_file_location("vdb_amd", os.path.join(PKG_DIR, "__init__.py"),
+                                                  submodule_search_locations=[PKG_DIR])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules["vdb_amd"] = mod
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--nlist", type=int, default=256)
+    ap.add_argument("--train", type=int, default=65536)
+    ap.add_argument("--queries", type=int, default=64)
+    ap.add_argument("--nprobe", type=int, default=16)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+    K = 10
+
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("range_bench needs a GPU: a time measured elsewhere says nothing")
+    vdb = load_vdb()
+    dev = torch.device("cuda:0")
+    lines = []
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        lines.append(line)
+
+    with torch.cuda.stream(torch.cuda.Stream(dev)):
+        s = torch.cuda.current_stream().cuda_stream
+        n, dim = args.n, args.dim
+        data = torch.empty((n, dim), dtype=torch.float32, device=dev)
+        vdb.gen_normal_device(data.data_ptr(), n * dim, seed=12345, stream=s)
+        ids = torch.arange(n, dtype=torch.int64, device=dev)
+        qd = torch.empty((args.queries, dim), dtype=torch.float32, device=dev)
+        vdb.gen_normal_device(qd.data_ptr(), qd.numel(), seed=999, stream=s)
+        torch.cuda.synchronize()
+        q = qd.cpu().numpy()
+
+        idx = vdb.IVFFlatIndex(vdb.IVFFlatIndex.Config(dim, args.nlist, vdb.Metric.L2, max_gpu_memory=0))
+        idx.set_batch(args.queries)
+        idx.train_device(data.data_ptr(), min(args.train, n))
+        idx.add_device(data.data_ptr(), ids.data_ptr(), n)
+        del data
+        emit({"what": "build", "n": n, "dim": dim, "nlist": args.nlist, "queries": args.queries,
+              "nprobe": args.nprobe, "k": K, "repeats": args.repeats, "build_id": vdb.build_id(),
+              "device": torch.cuda.get_device_name(0)})
+
+        def med(v):
+            return round(statistics.median(v), 3)
+
+        def plain(screen):
+            idx.set_option("screen", screen)
+            idx.search(q, nprobe=args.nprobe, k=K)  # warm-up (builds or drops the screen)
+            t = []
+            for _ in range(args.repeats):
+                t0 = time.perf_counter()
+                idx.search(q, nprobe=args.nprobe, k=K)
+                t.append((time.perf_counter() - t0) * 1e3)
+            emit({"what": "plain", "screen": screen, "wall_ms": med(t), "min": round(min(t), 3), "max": round(max(t), 3)})
+
+        # the radii, from a k = 10 search of the same queries and one +inf range search
+        idx.set_option("screen", 0)
+        D, _ = idx.search(q, nprobe=args.nprobe, k=K)
+        _, every, _ = idx.range_search(q, np.inf, nprobe=args.nprobe)
+        radii = [("no_hit", float(np.nextafter(D.min(), np.float32(-np.inf), dtype=np.float32))),
+                 ("median_10th", float(np.median(D[:, K - 1]))),
+                 ("1pct_of_probed", float(np.partition(every, every.size // 100)[every.size // 100])),
+                 ("inf", float("inf"))]
+        # the rows one read serves: per list cdiv(pairs, GROUP) reads of its rows (probes recomputed
+        # here in float64; a tie with the engine's fp32 choice moves a few rows at most)
+        C = idx.centroids.astype(np.float64)
+        d2 = (q.astype(np.float64) ** 2).sum(1)[:, None] - 2.0 * q.astype(np.float64) @ C.T + (C ** 2).sum(1)[None, :]
+        probes = np.argsort(d2, axis=1, kind="stable")[:, :min(args.nprobe, args.nlist)]
+        per_list = np.bincount(probes.ravel(), minlength=args.nlist)
+        sizes = idx.list_sizes().astype(np.int64)
+        rows_read = int((-(-per_list // GROUP) * sizes).sum())
+        dp = -(-dim // 64) * 64
+        emit({"what": "reads", "pairs_host": int((per_list * sizes).sum()), "rows_read": rows_read,
+              "group": round(float((per_list * sizes).sum()) / max(rows_read, 1), 3), "read_bytes": rows_read * dp * 4})
+
+        def ranged(layout):
+            for name, r in radii:
+                idx.range_search(q, r, nprobe=args.nprobe)
+                t, steps = [], []
+                for _ in range(args.repeats):
+                    t0 = time.perf_counter()
+                    idx.range_search(q, r, nprobe=args.nprobe)
+                    t.append((time.perf_counter() - t0) * 1e3)
+                    steps.append(idx.range_last_timing())
+                scan = med([x["scan_ms"] for x in steps])
+                passes = 1 + steps[-1]["reruns"]
+                emit({"what": "range", "layout": layout, "radius": name, "r": r, "wall_ms": med(t),
+                      "min": round(min(t), 3), "max": round(max(t), 3), "scan_ms": scan,
+                      "order_ms": med([x["order_ms"] for x in steps]), "pairs_scanned": steps[-1]["pairs_scanned"],
+                      "hits": steps[-1]["hits"], "reruns": steps[-1]["reruns"],
+                      "scan_TBps": round(rows_read * dp * 4 * passes / (scan * 1e-3) / 1e12, 3) if scan > 0 else None})
+
+        plain(0)
+        ranged("interleaved")
+        plain(1)
+        ranged("row-major")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
