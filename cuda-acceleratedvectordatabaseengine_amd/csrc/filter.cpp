@@ -8,8 +8,9 @@
 //
 // Nothing moves and nothing is rebuilt. Per call: mark (ivf_filter_mark: per 64-slot block an
 // allow mask, from the ids alone, and per list the allowed count), then per batch the handle's
-// own coarse step, the masked scan (ivf_filter_scan: blocks with an empty mask are skipped,
-// allowed lanes only) and the merge (ivf_filter_merge). The lists are read in the fp32 layout
+// own coarse step, the pairs grouped by list (launch_scan_group, the allowed counts as the gate),
+// the masked scan (ivf_filter_scan: blocks with an empty mask are skipped, allowed lanes only)
+// and the merge (ivf_filter_merge). The lists are read in the fp32 layout
 // the handle holds at that moment: the interleaved arena, or the screen's row-major copy while
 // the arena is dropped. Exact scan only: the screen's shadow bounds and thresholds describe
 // whole lists.
@@ -17,12 +18,14 @@
 // A free function over vdb_ivf's public members, as remove.cpp is and for the same reason: the
 // handle's header is one of the sources the build id hashes, and this feature touches no
 // existing scan kernel. It calls nothing that changes the handle: no screen_update,
-// screen_release, ensure_arena or upload_directory; the workspace is the call's own.
+// screen_release, ensure_arena or upload_directory; the workspace is the call's own. What it
+// shares with range.cpp (the refusals, the layout choice, the grouping buffers) is exact_call.hpp.
 #include "filter.hpp"
 
 #include <algorithm>
 #include <cfloat>
 
+#include "exact_call.hpp"
 #include "filter_kernels.hpp"
 #include "remove_plan.hpp"
 
@@ -71,46 +74,29 @@ struct BatchTimer {
     }
 };
 
-// The stream is idle before the call's buffers go and before the caller releases the mutex,
-// on every way out.
-struct StreamFence {
-    hipStream_t s;
-    ~StreamFence() { (void)hipStreamSynchronize(s); }
-};
-
 }  // namespace
 
 void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe, uint32_t k,
                      const std::vector<uint64_t>& sorted, bool include, float* distances, uint64_t* ids) {
     require(k <= vdbk::kFilterMaxK, "search_filtered serves k <= 64", VDB_ERR_UNSUPPORTED);
     require(sorted.size() < (1ull << 31), "more than 2^31 - 1 ids in one filter", VDB_ERR_UNSUPPORTED);
-    require(!h.is_group(), "search_filtered is not available on a group handle", VDB_ERR_UNSUPPORTED);
-    require(h.world == 1 && h.comm_world == 1,
-            "search_filtered is not available on a sharded handle (set_shard / plan_shard / a shard file / "
-            "attach_comm with world > 1)",
-            VDB_ERR_UNSUPPORTED);
-    require(!h.file_home(), "search_filtered is not available while the lists are served from a file (vdb_ivf_open_lists)",
-            VDB_ERR_UNSUPPORTED);
-    require(!h.tiered() && !h.arena.host,
-            "search_filtered is not available in the list-cache tier (list_cache_bytes, or max_gpu_memory exceeded)",
-            VDB_ERR_UNSUPPORTED);
+    require_resident_single(h, "search_filtered");
     g_filter_timing = FilterTiming{};
     if (n == 0 || k == 0) return;
-    const uint32_t P = std::min(nprobe, h.nlist);
-    require(P <= (uint32_t)vdbk::kMaxK, "nprobe above 1024 is not supported", VDB_ERR_UNSUPPORTED);
+    const uint32_t P = exact_probes(h, nprobe);
     const size_t nk = (size_t)n * k;
     auto all_unfilled = [&] {
         std::fill(distances, distances + nk, FLT_MAX);
         std::fill(ids, ids + nk, ~0ull);
     };
     if (P == 0 || h.arena_blocks == 0 || h.total == 0) return all_unfilled();
-    const float4* lists = h.arena_dropped ? (const float4*)h.screen_rows.p : h.arena.p;
-    require(lists != nullptr && h.arena_ids.p != nullptr, "the handle holds no fp32 copy of its lists", VDB_ERR_STATE);
+    (void)resident_lists(h);  // (refused before any device work)
 
     hipStream_t s = h.stream;
     const uint64_t nb = h.arena_blocks;
     DevBuf<uint64_t> d_sorted, d_out_i, d_slot_i, d_part_i, d_carry_i;
-    DevBuf<uint32_t> d_valid, d_allowed, d_cursor, d_pair_start, d_item_start, d_inv;
+    DevBuf<uint32_t> d_valid, d_allowed;
+    ScanGroupBufs grp;
     DevBuf<unsigned long long> d_allow, d_pairs;
     DevBuf<float> d_q, d_out_d, d_slot_d, d_part_d, d_carry_d;
     vdb_ivf::SearchSlot w;  // the call's own workspace, not one of the ring's
@@ -144,11 +130,8 @@ void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t npro
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(mark_ev[1], s));
 
-    // a list longer than kFilterSegBlocks blocks is cut into segments (the longest list's: the cap)
-    uint64_t longest = 0;
-    for (uint32_t l = 0; l < h.nlist; ++l)
-        if (h.owned[l]) longest = std::max(longest, cdiv(h.count[l], 64));
-    const uint32_t segs = vdbk::filter_segs((uint32_t)longest, vdbk::kFilterMaxSegs);
+    // a list longer than kScanSegBlocks blocks is cut into segments (the longest list's: the cap)
+    const uint32_t segs = vdbk::scan_seg_cap(h.count.data(), h.owned.data(), h.nlist);
 
     const uint32_t bmax = std::min(h.batch_cap(P, k), n);
     h.ensure_workspace(w, bmax, P, k);
@@ -161,10 +144,7 @@ void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t npro
     }
     d_out_d.ensure(nk);
     d_out_i.ensure(nk);
-    d_cursor.ensure(h.nlist);
-    d_pair_start.ensure((size_t)h.nlist + 1);
-    d_item_start.ensure((size_t)h.nlist + 1);
-    d_inv.ensure((size_t)bmax * P);
+    grp.ensure(h.nlist, (size_t)bmax * P);
     d_carry_d.ensure((size_t)P * k);
     HIPCHECK(hipMemsetAsync(d_carry_i.ensure((size_t)P * k), 0xFF, (size_t)P * k * 8, s));
 
@@ -175,26 +155,13 @@ void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t npro
         hipEvent_t* ev = timer.take();
         // 4. the masked exact scan: the pairs grouped by list, then one item per (list segment, 4 queries)
         HIPCHECK(hipEventRecord(ev[0], s));
-        vdbk::launch_filter_invert(w.probes.p, B * P, d_allowed.p, h.d_count_local.p, h.nlist, segs, d_cursor.p,
-                                   d_pair_start.p, d_item_start.p, d_inv.p, s);
+        vdbk::launch_scan_group(w.probes.p, B * P, d_allowed.p, h.d_count_local.p, h.nlist, segs, vdbk::kFilterGroup,
+                                grp.cursor.p, grp.pair_start.p, grp.item_start.p, grp.inv.p, s);
         HIPCHECK(hipGetLastError());
         vdbk::FilterScanArgs a;
-        a.lists = lists;
-        a.ids = h.arena_ids.p;
+        fill_scan_list_args(a, h, w, grp, B, P, segs);
         a.allow = d_allow.p;
-        a.block_off = h.d_block_off.p;
-        a.count = h.d_count_local.p;
-        a.q = w.q;
-        a.inv = d_inv.p;
-        a.pair_start = d_pair_start.p;
-        a.item_start = d_item_start.p;
-        a.nlist = h.nlist;
-        a.B = B;
-        a.P = P;
-        a.d4 = h.d4;
         a.k = k;
-        a.segs = segs;
-        a.rows = h.arena_dropped ? 1 : 0;
         a.part_d = segs > 1 ? d_part_d.p : d_slot_d.p;
         a.part_i = segs > 1 ? d_part_i.p : d_slot_i.p;
         vdbk::launch_filter_scan(h.metric, a, s);

@@ -5,8 +5,8 @@
 //   ivf_filter_mark   lane i looks its slot's id up in the call's sorted filter ids; the wave's
 //                     ballot is the block's 64-bit allow mask (pad slots never set).
 //   ivf_filter_count  per list the popcount of its blocks' masks.
-//   ivf_filter_pair_* the batch's (query, probe) pairs grouped by list (count, prefix, fill).
-//   ivf_filter_scan   one workgroup of 4 waves per item: one segment of one list against up to
+//   ivf_filter_scan   one workgroup of 4 waves per item of the pair grouping (scan_items.hip,
+//                     decoded by scan_items.hpp): one segment of one list against up to
 //                     4 of the queries that probe it (one read of a block feeds 4 distance
 //                     chains). The waves take the segment's blocks in turn, skip a block whose
 //                     mask is zero without touching its rows, and compute the exact distance
@@ -76,72 +76,6 @@ __global__ __launch_bounds__(kWaves * 64) void ivf_filter_count(const unsigned l
     if (lane_id() == 0) allowed[l] = sum;
 }
 
-__global__ void ivf_filter_pair_count(const uint32_t* __restrict__ probes, uint32_t BP,
-                                      const uint32_t* __restrict__ allowed, uint32_t* __restrict__ cursor) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= BP) return;
-    const uint32_t l = probes[i];
-    if (allowed[l]) atomicAdd(&cursor[l], 1u);
-}
-
-// One workgroup: exclusive prefixes over the lists of their pairs and of their scan items;
-// the per-list pair counts (cursor) are cleared for the fill pass.
-__global__ __launch_bounds__(256) void ivf_filter_prefix(uint32_t* __restrict__ cursor,
-                                                         const uint32_t* __restrict__ count, uint32_t nlist,
-                                                         uint32_t segs, uint32_t* __restrict__ pair_start,
-                                                         uint32_t* __restrict__ item_start) {
-    __shared__ uint32_t s_p[256], s_it[256];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t chunk = (nlist + 255) / 256;
-    const uint32_t lo = min(nlist, tid * chunk), hi = min(nlist, lo + chunk);
-    auto items = [&](uint32_t l, uint32_t c) {
-        return (c + kFilterGroup - 1) / kFilterGroup * filter_segs((count[l] + 63) >> 6, segs);
-    };
-    uint32_t p = 0, it = 0;
-    for (uint32_t l = lo; l < hi; ++l) {
-        const uint32_t c = cursor[l];
-        p += c;
-        it += items(l, c);
-    }
-    s_p[tid] = p;
-    s_it[tid] = it;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t ap = 0, ai = 0;
-        for (uint32_t t = 0; t < 256; ++t) {
-            const uint32_t vp = s_p[t], vi = s_it[t];
-            s_p[t] = ap;
-            s_it[t] = ai;
-            ap += vp;
-            ai += vi;
-        }
-    }
-    __syncthreads();
-    p = s_p[tid];
-    it = s_it[tid];
-    for (uint32_t l = lo; l < hi; ++l) {
-        const uint32_t c = cursor[l];
-        pair_start[l] = p;
-        item_start[l] = it;
-        p += c;
-        it += items(l, c);
-        cursor[l] = 0;
-    }
-    if (tid == 255) {  // (its chunk ends at nlist: the totals)
-        pair_start[nlist] = p;
-        item_start[nlist] = it;
-    }
-}
-
-__global__ void ivf_filter_pair_fill(const uint32_t* __restrict__ probes, uint32_t BP,
-                                     const uint32_t* __restrict__ allowed, const uint32_t* __restrict__ pair_start,
-                                     uint32_t* __restrict__ cursor, uint32_t* __restrict__ inv) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= BP) return;
-    const uint32_t l = probes[i];
-    if (allowed[l]) inv[pair_start[l] + atomicAdd(&cursor[l], 1u)] = i;
-}
-
 template <int M, bool ROWS>
 __global__ __launch_bounds__(kWaves * 64) void ivf_filter_scan(const FilterScanArgs a) {
     constexpr int G = (int)kFilterGroup;
@@ -154,25 +88,10 @@ __global__ __launch_bounds__(kWaves * 64) void ivf_filter_scan(const FilterScanA
     const int k = (int)a.k;
     const uint32_t total = a.item_start[a.nlist];
     for (uint32_t item = blockIdx.x; item < total; item += gridDim.x) {  // (the same in every wave)
-        uint32_t list = 0;
-        {
-            uint32_t lo = 0, hi = a.nlist;  // the first list whose items end beyond `item`
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (a.item_start[mid + 1] > item) hi = mid;
-                else lo = mid + 1;
-            }
-            list = lo;
-        }
-        const uint32_t r = item - a.item_start[list];
-        const uint32_t nb = (a.count[list] + 63) >> 6;
-        const uint32_t segs_l = filter_segs(nb, a.segs);
-        const uint32_t seg = r % segs_l, grp = r / segs_l;
-        const uint32_t p0 = a.pair_start[list] + grp * G;
-        const int np = (int)min((uint32_t)G, a.pair_start[list + 1] - p0);  // >= 1; slots g >= np repeat the last query
-        const uint32_t per = (nb + segs_l - 1) / segs_l;
-        const uint32_t b_lo = min(nb, seg * per), b_hi = min(nb, b_lo + per);
-        const uint64_t base = a.block_off[list];
+        const ExactScanItem it = decode_scan_item<kFilterGroup>(item, a.item_start, a.pair_start, a.count, a.nlist, a.segs);
+        const uint32_t seg = it.seg, p0 = it.p0, b_lo = it.b_lo, b_hi = it.b_hi;
+        const int np = (int)it.np;  // >= 1; slots g >= np repeat the last query
+        const uint64_t base = a.block_off[it.list];
         const float4* __restrict__ q4[G];  // (wave-uniform reads)
 #pragma unroll
         for (int g = 0; g < G; ++g)
@@ -269,7 +188,7 @@ __global__ __launch_bounds__(kWaves * 64) void ivf_filter_fold(const float* __re
     tk.init();
     float kd = __builtin_inff();
     uint64_t ki = kNoId;
-    const uint32_t n = filter_segs((count[list] + 63) >> 6, segs) * k;  // the list's segments are the pair's first
+    const uint32_t n = scan_segs((count[list] + 63) >> 6, segs) * k;  // the list's segments are the pair's first
     const size_t base = (size_t)i * segs * k;
     for (uint32_t e0 = 0; e0 < n; e0 += 64) {
         const uint32_t e = e0 + lane;
@@ -409,16 +328,6 @@ void launch_filter_scan(int metric, const FilterScanArgs& a, hipStream_t s) {
     if (metric == kL2) scan_metric<kL2>(a, s);
     else if (metric == kIP) scan_metric<kIP>(a, s);
     else scan_metric<kCos>(a, s);
-}
-
-void launch_filter_invert(const uint32_t* probes, uint32_t BP, const uint32_t* allowed, const uint32_t* count,
-                          uint32_t nlist, uint32_t segs, uint32_t* cursor, uint32_t* pair_start, uint32_t* item_start,
-                          uint32_t* inv, hipStream_t s) {
-    if (!BP || !nlist) return;
-    (void)hipMemsetAsync(cursor, 0, (size_t)nlist * 4, s);
-    ivf_filter_pair_count<<<(BP + 255) / 256, 256, 0, s>>>(probes, BP, allowed, cursor);
-    ivf_filter_prefix<<<1, 256, 0, s>>>(cursor, count, nlist, segs, pair_start, item_start);
-    ivf_filter_pair_fill<<<(BP + 255) / 256, 256, 0, s>>>(probes, BP, allowed, pair_start, cursor, inv);
 }
 
 void launch_filter_fold(const float* part_d, const uint64_t* part_i, const uint32_t* probes, const uint32_t* allowed,

@@ -2,22 +2,12 @@
 // (filter_kernels.hip, gfx950, wave64).
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "scan_kernels.hpp"
 
 namespace vdbk {
 
-constexpr uint32_t kFilterMaxK = 64;        // one top-k register per lane (WaveTopK<1>)
-constexpr uint32_t kFilterSegBlocks = 16;   // a list longer than this many blocks is cut into segments ...
-constexpr uint32_t kFilterMaxSegs = 16;     // ... at most this many
-constexpr uint32_t kFilterGroup = 4;        // queries that probe the same list share one read of it
-
-// Segments a list of nb blocks is cut into, under the call's cap (the segments of its longest list).
-__host__ __device__ inline uint32_t filter_segs(uint32_t nb, uint32_t cap) {
-    const uint32_t s = (nb + kFilterSegBlocks - 1) / kFilterSegBlocks;
-    return s < 1 ? 1 : (s > cap ? cap : s);
-}
+constexpr uint32_t kFilterMaxK = 64;   // one top-k register per lane (WaveTopK<1>)
+constexpr uint32_t kFilterGroup = 4;   // queries that probe the same list share one read of it
 
 // allow[b] bit i = slot i of block b holds a row (i < valid[b]) that the filter lets through:
 // include == 0: its id is not one of sorted[0..n); include != 0: it is. sorted is ascending,
@@ -30,33 +20,15 @@ void launch_filter_mark(const uint64_t* arena_ids, const uint32_t* valid, uint64
 void launch_filter_count(const unsigned long long* allow, const uint64_t* block_off, const uint32_t* count,
                          uint32_t nlist, uint32_t* allowed, hipStream_t s);
 
-// The batch's (query, probe) pairs grouped by probed list, pairs of a list with no allowed row
-// left out: inv[pair_start[l] .. pair_start[l + 1]) are the pairs (q * P + p) that probe list l
-// (in no particular order: every pair's result is computed on its own). item_start[l] is the
-// first scan item of list l: a list has cdiv(pairs, kFilterGroup) x filter_segs(blocks, segs)
-// items; item_start[nlist] is their number. cursor is scratch ([nlist]).
-void launch_filter_invert(const uint32_t* probes, uint32_t BP, const uint32_t* allowed, const uint32_t* count,
-                          uint32_t nlist, uint32_t segs, uint32_t* cursor, uint32_t* pair_start, uint32_t* item_start,
-                          uint32_t* inv, hipStream_t s);
-
-struct FilterScanArgs {
-    const float4* lists = nullptr;  // rows == 0: [block][d4][64] float4; rows != 0: [slot][d4] float4
-    const uint64_t* ids = nullptr;  // [block][64]
+struct FilterScanArgs : ScanListArgs {
+    uint32_t k = 0;
     const unsigned long long* allow = nullptr;  // per arena block
-    const uint64_t* block_off = nullptr;        // per list
-    const uint32_t* count = nullptr;            // per list
-    const float* q = nullptr;                   // the batch's padded queries [B][d4 * 4]
-    const uint32_t* inv = nullptr;              // launch_filter_invert
-    const uint32_t* pair_start = nullptr;
-    const uint32_t* item_start = nullptr;
-    uint32_t nlist = 0, B = 0, P = 0, d4 = 0, k = 0;
-    uint32_t segs = 1;   // the call's segment cap (1 .. kFilterMaxSegs)
-    int rows = 0;
     float* part_d = nullptr;  // [B * P][segs][k]: per segment the top-k of its allowed rows
     uint64_t* part_i = nullptr;
 };
-// One workgroup per item: one segment of one list against up to kFilterGroup of the queries
-// that probe it. A pair whose list has no allowed row gets no item and nothing is written for it.
+// One workgroup per item of launch_scan_group (group kFilterGroup, gate = the lists' allowed
+// rows): one segment of one list against up to kFilterGroup of the queries that probe it. A
+// pair whose list has no allowed row gets no item and nothing is written for it.
 void launch_filter_scan(int metric, const FilterScanArgs& a, hipStream_t s);
 
 // segs > 1: per pair the top-k of its segments' partials into slot_d / slot_i [B * P][k].

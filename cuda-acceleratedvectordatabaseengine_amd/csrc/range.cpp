@@ -8,7 +8,7 @@
 // smallest distance, ascending by (distance, id). A query answered alone has no stale slot, so
 // the result depends on neither stale_slots nor batch.
 //
-// Per batch: the handle's own coarse step, the pairs grouped by list (launch_range_group: eight
+// Per batch: the handle's own coarse step, the pairs grouped by list (launch_scan_group: eight
 // queries share one read of a list), the thresholded scan (ivf_range_scan: hits appended
 // to a buffer through one global cursor) and the ordering on the device (three stable radix
 // sorts around range_dedup, then range_finish). The size of a batch's result is known only
@@ -19,13 +19,14 @@
 //
 // A free function over vdb_ivf's public members, as filter.cpp is and for the same reason. It
 // calls nothing that changes the handle: no screen_update, screen_release, ensure_arena or
-// upload_directory; the workspace is the call's own.
+// upload_directory; the workspace is the call's own. What it shares with filter.cpp (the
+// refusals, the layout choice, the grouping buffers) is exact_call.hpp.
 #include "range.hpp"
 
 #include <algorithm>
 #include <cmath>
 
-#include "filter_kernels.hpp"
+#include "exact_call.hpp"
 #include "range_kernels.hpp"
 
 namespace vdbe {
@@ -48,13 +49,6 @@ struct Events {
         HIPCHECK(hipEventElapsedTime(&t, e[a], e[b]));
         return t;
     }
-};
-
-// The stream is idle before the call's buffers go and before the caller releases the mutex,
-// on every way out.
-struct StreamFence {
-    hipStream_t s;
-    ~StreamFence() { (void)hipStreamSynchronize(s); }
 };
 
 // The device buffers that hold and order a batch's hits: one allocation, cut into the four
@@ -87,29 +81,19 @@ struct HitBufs {
 std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe,
                                                float radius, uint64_t reserve) {
     require(!std::isnan(radius), "the radius is NaN");
-    require(!h.is_group(), "range_search is not available on a group handle", VDB_ERR_UNSUPPORTED);
-    require(h.world == 1 && h.comm_world == 1,
-            "range_search is not available on a sharded handle (set_shard / plan_shard / a shard file / "
-            "attach_comm with world > 1)",
-            VDB_ERR_UNSUPPORTED);
-    require(!h.file_home(), "range_search is not available while the lists are served from a file (vdb_ivf_open_lists)",
-            VDB_ERR_UNSUPPORTED);
-    require(!h.tiered() && !h.arena.host,
-            "range_search is not available in the list-cache tier (list_cache_bytes, or max_gpu_memory exceeded)",
-            VDB_ERR_UNSUPPORTED);
+    require_resident_single(h, "range_search");
     g_range_timing = RangeTiming{};
     auto res = std::make_unique<vdb_range_result>();
     res->n = n;
     res->lims.assign((size_t)n + 1, 0);
     if (n == 0) return res;
-    const uint32_t P = std::min(nprobe, h.nlist);
-    require(P <= (uint32_t)vdbk::kMaxK, "nprobe above 1024 is not supported", VDB_ERR_UNSUPPORTED);
+    const uint32_t P = exact_probes(h, nprobe);
     if (P == 0 || h.arena_blocks == 0 || h.total == 0) return res;
-    const float4* lists = h.arena_dropped ? (const float4*)h.screen_rows.p : h.arena.p;
-    require(lists != nullptr && h.arena_ids.p != nullptr, "the handle holds no fp32 copy of its lists", VDB_ERR_STATE);
+    (void)resident_lists(h);  // (refused before any device work)
 
     hipStream_t s = h.stream;
-    DevBuf<uint32_t> d_cursor, d_pair_start, d_item_start, d_inv, d_start;
+    DevBuf<uint32_t> d_start;
+    ScanGroupBufs grp;
     DevBuf<unsigned long long> d_ctrl;
     DevBuf<float> d_q;
     HitBufs hit;
@@ -119,18 +103,12 @@ std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries,
 
     HIPCHECK(hipMemcpyAsync(d_q.ensure((size_t)n * h.dim), queries, (size_t)n * h.dim * 4, hipMemcpyHostToDevice, s));
 
-    // a list longer than kFilterSegBlocks blocks is cut into segments (the longest list's: the cap)
-    uint64_t longest = 0;
-    for (uint32_t l = 0; l < h.nlist; ++l)
-        if (h.owned[l]) longest = std::max(longest, cdiv(h.count[l], 64));
-    const uint32_t segs = vdbk::filter_segs((uint32_t)longest, vdbk::kFilterMaxSegs);
+    // a list longer than kScanSegBlocks blocks is cut into segments (the longest list's: the cap)
+    const uint32_t segs = vdbk::scan_seg_cap(h.count.data(), h.owned.data(), h.nlist);
 
     const uint32_t bmax = std::min(h.batch_cap(P, 1), n);
     h.ensure_workspace(w, bmax, P, 1);
-    d_cursor.ensure(h.nlist);
-    d_pair_start.ensure((size_t)h.nlist + 1);
-    d_item_start.ensure((size_t)h.nlist + 1);
-    d_inv.ensure((size_t)bmax * P);
+    grp.ensure(h.nlist, (size_t)bmax * P);
     d_start.ensure((size_t)bmax + 1);
     d_ctrl.ensure(vdbk::kRangeCtrlWords);
     hit.ensure(std::min<uint64_t>(reserve ? reserve : kRangeAutoReserve, (1ull << 31) - 1), bmax);
@@ -142,27 +120,14 @@ std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries,
         HIPCHECK(hipGetLastError());
         // 2. the pairs grouped by list, one item per (list segment, 8 queries); empty lists get none
         HIPCHECK(hipEventRecord(ev.e[0], s));
-        vdbk::launch_range_group(w.probes.p, B * P, h.d_count_local.p, h.nlist, segs, d_cursor.p, d_pair_start.p,
-                                 d_item_start.p, d_inv.p, s);
+        vdbk::launch_scan_group(w.probes.p, B * P, h.d_count_local.p, h.d_count_local.p, h.nlist, segs,
+                                vdbk::kRangeGroup, grp.cursor.p, grp.pair_start.p, grp.item_start.p, grp.inv.p, s);
         HIPCHECK(hipGetLastError());
         // 3. the thresholded scan, once more if the hits did not fit
         unsigned long long ctrl[vdbk::kRangeCtrlWords] = {};
         for (int pass = 0;; ++pass) {
             vdbk::RangeScanArgs a;
-            a.lists = lists;
-            a.ids = h.arena_ids.p;
-            a.block_off = h.d_block_off.p;
-            a.count = h.d_count_local.p;
-            a.q = w.q;
-            a.inv = d_inv.p;
-            a.pair_start = d_pair_start.p;
-            a.item_start = d_item_start.p;
-            a.nlist = h.nlist;
-            a.B = B;
-            a.P = P;
-            a.d4 = h.d4;
-            a.segs = segs;
-            a.rows = h.arena_dropped ? 1 : 0;
+            fill_scan_list_args(a, h, w, grp, B, P, segs);
             a.radius = radius;
             a.cap = hit.cap;
             a.hit_key = hit.key_a;

@@ -2,9 +2,8 @@
 //
 // The list arena is cut into blocks of 64 slots with the ids beside it, so one wavefront
 // handles one block and lane i owns slot i, as in filter_kernels.hip.
-//   range_pair_*      the batch's (query, probe) pairs grouped by list (count, prefix, fill), as
-//                     ivf_filter_pair_* with a group of 8 and the lists' counts as the filter.
-//   ivf_range_scan    persistent workgroups of 4 waves over the items of launch_range_group:
+//   ivf_range_scan    persistent workgroups of 4 waves over the items of the pair grouping
+//                     (scan_items.hip with a group of 8, decoded by scan_items.hpp):
 //                     one segment of one list against up to 8 of the queries that probe it (one
 //                     read of a block feeds 8 distance chains, 4 for a group of at most 4). A
 //                     workgroup takes its next item from one device counter. The waves take the
@@ -36,7 +35,6 @@
 
 #include <algorithm>
 
-#include "filter_kernels.hpp"
 #include "scan_common.hpp"
 #include "wave_topk.hpp"
 
@@ -52,72 +50,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__global__ void range_pair_count(const uint32_t* __restrict__ probes, uint32_t BP, const uint32_t* __restrict__ count,
-                                 uint32_t* __restrict__ cursor) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= BP) return;
-    const uint32_t l = probes[i];
-    if (count[l]) atomicAdd(&cursor[l], 1u);
-}
-
-// One workgroup: exclusive prefixes over the lists of their pairs and of their scan items;
-// the per-list pair counts (cursor) are cleared for the fill pass.
-__global__ __launch_bounds__(256) void range_pair_prefix(uint32_t* __restrict__ cursor,
-                                                         const uint32_t* __restrict__ count, uint32_t nlist,
-                                                         uint32_t segs, uint32_t* __restrict__ pair_start,
-                                                         uint32_t* __restrict__ item_start) {
-    __shared__ uint32_t s_p[256], s_it[256];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t chunk = (nlist + 255) / 256;
-    const uint32_t lo = min(nlist, tid * chunk), hi = min(nlist, lo + chunk);
-    auto items = [&](uint32_t l, uint32_t c) {
-        return (c + kRangeGroup - 1) / kRangeGroup * filter_segs((count[l] + 63) >> 6, segs);
-    };
-    uint32_t p = 0, it = 0;
-    for (uint32_t l = lo; l < hi; ++l) {
-        const uint32_t c = cursor[l];
-        p += c;
-        it += items(l, c);
-    }
-    s_p[tid] = p;
-    s_it[tid] = it;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t ap = 0, ai = 0;
-        for (uint32_t t = 0; t < 256; ++t) {
-            const uint32_t vp = s_p[t], vi = s_it[t];
-            s_p[t] = ap;
-            s_it[t] = ai;
-            ap += vp;
-            ai += vi;
-        }
-    }
-    __syncthreads();
-    p = s_p[tid];
-    it = s_it[tid];
-    for (uint32_t l = lo; l < hi; ++l) {
-        const uint32_t c = cursor[l];
-        pair_start[l] = p;
-        item_start[l] = it;
-        p += c;
-        it += items(l, c);
-        cursor[l] = 0;
-    }
-    if (tid == 255) {  // (its chunk ends at nlist: the totals)
-        pair_start[nlist] = p;
-        item_start[nlist] = it;
-    }
-}
-
-__global__ void range_pair_fill(const uint32_t* __restrict__ probes, uint32_t BP, const uint32_t* __restrict__ count,
-                                const uint32_t* __restrict__ pair_start, uint32_t* __restrict__ cursor,
-                                uint32_t* __restrict__ inv) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= BP) return;
-    const uint32_t l = probes[i];
-    if (count[l]) inv[pair_start[l] + atomicAdd(&cursor[l], 1u)] = i;
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -240,30 +172,15 @@ __global__ __launch_bounds__(kWaves * 64) void ivf_range_scan(const RangeScanArg
         const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_item);  // (the same in every wave)
         __syncthreads();               // (read by all before thread 0 writes the next)
         if (item >= total) break;
-        uint32_t list = 0;
-        {
-            uint32_t lo = 0, hi = a.nlist;  // the first list whose items end beyond `item`
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (a.item_start[mid + 1] > item) hi = mid;
-                else lo = mid + 1;
-            }
-            list = lo;
-        }
-        const uint32_t r = item - a.item_start[list];
-        const uint32_t cnt = a.count[list];
-        const uint32_t nb = (cnt + 63) >> 6;
-        const uint32_t segs_l = filter_segs(nb, a.segs);
-        const uint32_t seg = r % segs_l, grp = r / segs_l;
-        const uint32_t p0 = a.pair_start[list] + grp * G;
-        const int np = (int)min((uint32_t)G, a.pair_start[list + 1] - p0);  // >= 1; slots g >= np repeat the last query
-        const uint32_t per = (nb + segs_l - 1) / segs_l;
-        const uint32_t b_lo = min(nb, seg * per), b_hi = min(nb, b_lo + per);
-        const uint64_t base = a.block_off[list];
-        if (seg == 0 && threadIdx.x == 0) atomicAdd(a.ctrl + kRangePairs, (unsigned long long)np * cnt);
+        const ExactScanItem it = decode_scan_item<kRangeGroup>(item, a.item_start, a.pair_start, a.count, a.nlist, a.segs);
+        const int np = (int)it.np;  // >= 1; slots g >= np repeat the last query
+        const uint32_t cnt = a.count[it.list];
+        const uint64_t base = a.block_off[it.list];
+        if (it.seg == 0 && threadIdx.x == 0) atomicAdd(a.ctrl + kRangePairs, (unsigned long long)np * cnt);
         // (half the chains for a short group: a list few of the batch's queries probe)
-        if (np <= G / 2) range_scan_blocks<M, ROWS, G / 2>(a, s_x[ROWS ? wave : 0], p0, np, b_lo, b_hi, base, cnt);
-        else range_scan_blocks<M, ROWS, G>(a, s_x[ROWS ? wave : 0], p0, np, b_lo, b_hi, base, cnt);
+        if (np <= G / 2)
+            range_scan_blocks<M, ROWS, G / 2>(a, s_x[ROWS ? wave : 0], it.p0, np, it.b_lo, it.b_hi, base, cnt);
+        else range_scan_blocks<M, ROWS, G>(a, s_x[ROWS ? wave : 0], it.p0, np, it.b_lo, it.b_hi, base, cnt);
     }
 }
 
@@ -319,15 +236,6 @@ int key_bits(uint32_t B) {
 }
 
 }  // namespace
-
-void launch_range_group(const uint32_t* probes, uint32_t BP, const uint32_t* count, uint32_t nlist, uint32_t segs,
-                        uint32_t* cursor, uint32_t* pair_start, uint32_t* item_start, uint32_t* inv, hipStream_t s) {
-    if (!BP || !nlist) return;
-    (void)hipMemsetAsync(cursor, 0, (size_t)nlist * 4, s);
-    range_pair_count<<<(BP + 255) / 256, 256, 0, s>>>(probes, BP, count, cursor);
-    range_pair_prefix<<<1, 256, 0, s>>>(cursor, count, nlist, segs, pair_start, item_start);
-    range_pair_fill<<<(BP + 255) / 256, 256, 0, s>>>(probes, BP, count, pair_start, cursor, inv);
-}
 
 void launch_range_scan(int metric, const RangeScanArgs& a, hipStream_t s) {
     if (!a.B || !a.P) return;

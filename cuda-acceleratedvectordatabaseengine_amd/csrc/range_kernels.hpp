@@ -2,9 +2,7 @@
 // (range_kernels.hip, gfx950, wave64).
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "scan_kernels.hpp"
 
 namespace vdbk {
 
@@ -15,26 +13,7 @@ constexpr uint32_t kRangeChunk4 = 8;  // row-major layout: float4 of a row stage
 enum { kRangeCursor = 0, kRangeStatus = 1, kRangePairs = 2, kRangeNext = 3, kRangeCtrlWords = 4 };  // (kRangeNext: the scan's item counter)
 constexpr unsigned long long kRangeUnserved = 1;  // status bit: a device guard refused the launch's shape
 
-// The batch's (query, probe) pairs grouped by probed list, pairs of an empty list left out:
-// inv[pair_start[l] .. pair_start[l + 1]) are the pairs (q * P + p) that probe list l, in no
-// particular order. item_start[l] is the first scan item of list l: a list has
-// cdiv(pairs, kRangeGroup) x filter_segs(blocks, segs) items; item_start[nlist] is their
-// number. cursor is scratch ([nlist]). (launch_filter_invert with a group of kRangeGroup.)
-void launch_range_group(const uint32_t* probes, uint32_t BP, const uint32_t* count, uint32_t nlist, uint32_t segs,
-                        uint32_t* cursor, uint32_t* pair_start, uint32_t* item_start, uint32_t* inv, hipStream_t s);
-
-struct RangeScanArgs {
-    const float4* lists = nullptr;  // rows == 0: [block][d4][64] float4; rows != 0: [slot][d4] float4
-    const uint64_t* ids = nullptr;  // [block][64]
-    const uint64_t* block_off = nullptr;  // per list
-    const uint32_t* count = nullptr;      // per list
-    const float* q = nullptr;             // the batch's padded queries [B][d4 * 4]
-    const uint32_t* inv = nullptr;        // launch_range_group
-    const uint32_t* pair_start = nullptr;
-    const uint32_t* item_start = nullptr;
-    uint32_t nlist = 0, B = 0, P = 0, d4 = 0;
-    uint32_t segs = 1;  // the call's segment cap (1 .. kFilterMaxSegs)
-    int rows = 0;
+struct RangeScanArgs : ScanListArgs {
     float radius = 0.0f;
     uint64_t cap = 0;             // entries hit_key / hit_id hold
     uint64_t* hit_key = nullptr;  // (batch query << 32) | ord_enc(distance)
@@ -45,8 +24,8 @@ struct RangeScanArgs {
 // kRangeChunk4 float4 per row). The kernel checks the same and sets kRangeUnserved.
 inline bool range_scan_serves(const RangeScanArgs& a) { return a.d4 > 0 && a.d4 % kRangeChunk4 == 0; }
 
-// Persistent workgroups over the items of launch_range_group: one segment of one list against
-// up to kRangeGroup of the queries that probe it. Every slot below its block's valid count
+// Persistent workgroups over the items of launch_scan_group (group kRangeGroup, gate = the
+// lists' counts): one segment of one list against up to kRangeGroup of the queries that probe it. Every slot below its block's valid count
 // whose exact distance d satisfies d <= radius is appended at ctrl[kRangeCursor] (one atomic
 // per wave and query); past `cap` nothing is written and the cursor keeps counting.
 // ctrl[kRangePairs] grows by the (query, row) distances computed.
