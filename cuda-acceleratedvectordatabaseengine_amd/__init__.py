@@ -130,6 +130,17 @@ def lib() -> ctypes.CDLL:
         "vdb_range_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                                                  ctypes.POINTER(ctypes.c_uint32)]),
+        "vdb_ivf_filter_create": (ctypes.c_int, [vp, vp, u64, ctypes.c_int, ctypes.POINTER(vp)]),
+        "vdb_ivf_filter_create_device": (ctypes.c_int, [vp, vp, u64, ctypes.c_int, ctypes.POINTER(vp)]),
+        "vdb_filter_combine": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(vp)]),
+        "vdb_filter_allowed": (u64, [vp]),
+        "vdb_filter_stale": (ctypes.c_int, [vp]),
+        "vdb_filter_free": (None, [vp]),
+        "vdb_ivf_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, vp]),
+        "vdb_ivf_range_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, ctypes.c_float, u64,
+                                                         ctypes.POINTER(vp)]),
+        "vdb_filter_create_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double),
+                                                         ctypes.POINTER(ctypes.c_double)]),
         "vdb_ivf_search_device": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "vdb_ivf_set_shard": (ctypes.c_int, [vp, u32, u32]),
         "vdb_ivf_plan_shard": (ctypes.c_int, [vp, u32, u32, vp]),
@@ -267,6 +278,57 @@ def merge_ranks_packed_device(records_ptr: int, nranks: int, n: int, k: int, out
     _check(lib().vdb_merge_ranks_packed_device(ctypes.c_void_p(records_ptr), nranks, n, k,
                                                ctypes.c_void_p(out_dist_ptr), ctypes.c_void_p(out_ids_ptr),
                                                ctypes.c_void_p(stream or 0)))
+
+
+FILTER_AND, FILTER_OR, FILTER_ANDNOT = 0, 1, 2  # VDB_FILTER_AND / _OR / _ANDNOT
+
+
+class Filter:
+    """A prepared id filter (vdb_filter; not in the reference): the allow masks of one index's
+    rows, kept on the device for any number of search_prepared / range_search_prepared calls.
+    Made by IVFFlatIndex.prepare_filter or by combining two filters of one index: ``a & b``,
+    ``a | b``, ``a.andnot(b)``. It may outlive its index; it is stale once the index's rows
+    changed (add, a remove that removed, load, ...) or the index is gone."""
+
+    def __init__(self, handle):
+        self._f = handle
+
+    @property
+    def allowed(self) -> int:
+        """Stored rows the filter lets through."""
+        return int(lib().vdb_filter_allowed(self._f))
+
+    @property
+    def stale(self) -> bool:
+        return bool(lib().vdb_filter_stale(self._f))
+
+    def _combine(self, other: "Filter", op: int) -> "Filter":
+        if not isinstance(other, Filter):
+            return NotImplemented
+        out = ctypes.c_void_p()
+        _check(lib().vdb_filter_combine(self._f, other._f, op, ctypes.byref(out)))
+        return Filter(out)
+
+    def __and__(self, other):
+        return self._combine(other, FILTER_AND)
+
+    def __or__(self, other):
+        return self._combine(other, FILTER_OR)
+
+    def andnot(self, other: "Filter") -> "Filter":
+        """The rows this filter allows and `other` does not."""
+        return self._combine(other, FILTER_ANDNOT)
+
+    def close(self):
+        if getattr(self, "_f", None):
+            lib().vdb_filter_free(self._f)
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class IVFFlatIndex:
@@ -415,6 +477,51 @@ class IVFFlatIndex:
         _check(lib().vdb_filter_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
         return {"mark_ms": a.value, "scan_ms": b.value, "merge_ms": c.value, "pairs_scanned": r.value}
 
+    def prepare_filter(self, ids, include: bool = False, *, device_ptr: int | None = None, n: int = 0) -> Filter:
+        """The id filter of search_filtered, prepared once (vdb_ivf_filter_create; not in the
+        reference). include=False: every row whose id is not in `ids`; include=True: only rows
+        whose id is. With device_ptr, the n uint64 ids are read from that address on the index's
+        device (vdb_ivf_filter_create_device) and `ids` is ignored."""
+        out = ctypes.c_void_p()
+        mode = 1 if include else 0
+        if device_ptr is not None:
+            _check(lib().vdb_ivf_filter_create_device(self._h, ctypes.c_void_p(device_ptr), n, mode, ctypes.byref(out)))
+        else:
+            f = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+            _check(lib().vdb_ivf_filter_create(self._h, _ptr(f), f.shape[0], mode, ctypes.byref(out)))
+        return Filter(out)
+
+    def filter_create_last_timing(self) -> dict:
+        """The calling thread's latest prepare_filter by step (vdb_filter_create_last_timing)."""
+        a, b = ctypes.c_double(0), ctypes.c_double(0)
+        _check(lib().vdb_filter_create_last_timing(ctypes.byref(a), ctypes.byref(b)))
+        return {"sort_ms": a.value, "mark_ms": b.value}
+
+    def search_prepared(self, queries: np.ndarray, flt: Filter, params: "IVFFlatIndex.SearchParams | None" = None, *,
+                        nprobe: int | None = None, k: int | None = None):
+        """search_filtered's result for the filter's rows, without taking the masks again
+        (vdb_ivf_search_prepared). Returns (distances, indices)."""
+        p = params or IVFFlatIndex.SearchParams()
+        nprobe = p.nprobe if nprobe is None else nprobe
+        k = p.k if k is None else k
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
+        n = q.shape[0]
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.uint64)
+        _check(lib().vdb_ivf_search_prepared(self._h, flt._f, _ptr(q), n, nprobe, k, _ptr(D), _ptr(I)))
+        return D, I
+
+    def range_search_prepared(self, queries: np.ndarray, flt: "Filter | None", radius: float, *, nprobe: int = 10,
+                              reserve: int = 0):
+        """range_search over the rows the filter allows (vdb_ivf_range_search_prepared): the
+        result range_search gives on an index holding only those rows. flt=None: range_search.
+        Returns (lims, distances, ids)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
+        r = ctypes.c_void_p()
+        _check(lib().vdb_ivf_range_search_prepared(self._h, flt._f if flt is not None else None, _ptr(q), q.shape[0],
+                                                   nprobe, float(radius), reserve, ctypes.byref(r)))
+        return self._take_range_result(r, q.shape[0])
+
     def range_search(self, queries: np.ndarray, radius: float, *, nprobe: int = 10, reserve: int = 0):
         """Every stored row within `radius` of each query among the lists it probes
         (vdb_ivf_range_search; not in the reference). Returns (lims, distances, ids): query i
@@ -426,6 +533,12 @@ class IVFFlatIndex:
         L = lib()
         r = ctypes.c_void_p()
         _check(L.vdb_ivf_range_search(self._h, _ptr(q), n, nprobe, float(radius), reserve, ctypes.byref(r)))
+        return self._take_range_result(r, n)
+
+    @staticmethod
+    def _take_range_result(r, n: int):
+        """A vdb_range_result into (lims, distances, ids) arrays of the caller's, then released."""
+        L = lib()
         try:
             lims = np.ctypeslib.as_array(ctypes.cast(L.vdb_range_result_lims(r), ctypes.POINTER(ctypes.c_uint64)),
                                          shape=(n + 1,)).copy()

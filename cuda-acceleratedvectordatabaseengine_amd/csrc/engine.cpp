@@ -5,6 +5,8 @@
 #include <cmath>
 
 #include "filter.hpp"
+#include "filter_epoch.hpp"
+#include "prepared.hpp"
 #include "range.hpp"
 #include "remove.hpp"
 #include "remove_plan.hpp"
@@ -27,6 +29,11 @@ uint64_t remove_ids(vdb_ivf* g, const std::vector<uint64_t>& sorted);
 inline void no_group(const vdb_ivf* h, const char* what) {
     require(!h->is_group(), std::string(what) + " is not available on a group handle", VDB_ERR_UNSUPPORTED);
 }
+
+// The entry points below that can change which stored row sits in which arena slot call this
+// under the handle's lock, before they start: every prepared filter of the handle is stale from
+// then on, whether the call succeeds or not (filter_epoch.hpp; the list is in DESIGN 7f).
+inline void rows_may_move(const vdb_ivf* h) { filter_epochs().bump(h); }
 }  // namespace vdbe
 
 extern "C" {
@@ -90,6 +97,7 @@ int vdb_ivf_create(const vdb_ivf_config* cfg, vdb_ivf** out) {
 int vdb_ivf_destroy(vdb_ivf* h) {
     return guarded([&] {
         if (!h) return;
+        filter_epochs().erase(h);  // (its filters are stale and never read it again)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         delete h;
@@ -150,6 +158,7 @@ int vdb_ivf_add(vdb_ivf* h, const float* v, const uint64_t* ids, uint64_t n) {
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         if (n == 0) return;
+        rows_may_move(h);
         if (h->is_group()) return group::add_host(h, v, ids, nullptr, n);
         DevBuf<float> dv;
         DevBuf<uint64_t> di;
@@ -165,6 +174,7 @@ int vdb_ivf_add_device(vdb_ivf* h, const float* d_v, const uint64_t* d_ids, uint
         require(h && ((d_v && d_ids) || n == 0), "null argument");
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
+        rows_may_move(h);
         if (h->is_group()) return group::add_device(h, d_v, d_ids, nullptr, n);
         h->add(d_v, d_ids, n);
         HIPCHECK(hipStreamSynchronize(h->stream));
@@ -176,6 +186,7 @@ int vdb_ivf_add_to_lists(vdb_ivf* h, const float* v, const uint64_t* ids, const 
         require(h && ((v && ids && lists) || n == 0), "null argument");
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
+        rows_may_move(h);
         if (h->is_group()) return group::add_host(h, v, ids, lists, n);
         h->add_to_lists_host(v, ids, lists, n);
     });
@@ -203,6 +214,7 @@ int vdb_ivf_add_to_lists_device(vdb_ivf* h, const float* d_v, const uint64_t* d_
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         if (n == 0) return;
+        rows_may_move(h);
         if (h->is_group()) return group::add_device(h, d_v, d_ids, d_lists, n);
         // The grouping kernels index per-list arrays by these ids: check them first.
         std::vector<uint32_t> hl(n);
@@ -229,7 +241,17 @@ int vdb_ivf_remove_ids(vdb_ivf* h, const uint64_t* ids, uint64_t n, uint64_t* re
                 VDB_ERR_UNSUPPORTED);
         h->set_device();
         const std::vector<uint64_t> sorted = remove_sorted_ids(ids, n);
+        // (a remove that matched nothing leaves the handle, and so its filters, untouched; one
+        // that throws may have got anywhere)
+        struct Moved {
+            vdb_ivf* h;
+            bool yes = true;
+            ~Moved() {
+                if (yes) rows_may_move(h);
+            }
+        } moved{h};
         const uint64_t gone = h->is_group() ? group::remove_ids(h, sorted) : remove_ids(*h, sorted, nullptr);
+        moved.yes = gone != 0;
         if (removed) *removed = gone;
     });
 }
@@ -248,6 +270,7 @@ int vdb_ivf_plan_shard(vdb_ivf* h, uint32_t rank, uint32_t world, const uint64_t
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         no_group(h, "plan_shard");
+        rows_may_move(h);
         h->plan_shard(rank, world, final_sizes);
     });
 }
@@ -375,6 +398,7 @@ int vdb_ivf_load(vdb_ivf* h, const char* path) {
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         require(h->total == 0, "load() needs an empty index (this one holds vectors)", VDB_ERR_STATE);
+        rows_may_move(h);
         std::vector<float> old((size_t)h->nlist * h->dim);
         h->head()->set_device();
         h->head()->export_centroids(old.data());
@@ -460,6 +484,83 @@ int vdb_range_last_timing(double* scan_ms, double* order_ms, uint64_t* pairs_sca
     return VDB_OK;
 }
 
+static int filter_create_entry(vdb_ivf* h, const uint64_t* filter_ids, uint64_t n_filter, int mode, vdb_filter** out,
+                               bool device_ids) {
+    return guarded([&] {
+        require(h && out && (filter_ids || n_filter == 0), "null argument");  // (before any device call)
+        require(mode == VDB_FILTER_EXCLUDE || mode == VDB_FILTER_INCLUDE, "invalid filter mode");
+        require(n_filter < (1ull << 31), "more than 2^31 - 1 ids in one filter", VDB_ERR_UNSUPPORTED);
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        *out = filter_create(*h, filter_ids, n_filter, mode == VDB_FILTER_INCLUDE, device_ids).release();
+    });
+}
+
+int vdb_ivf_filter_create(vdb_ivf* h, const uint64_t* filter_ids, uint64_t n_filter, int mode, vdb_filter** out) {
+    return filter_create_entry(h, filter_ids, n_filter, mode, out, false);
+}
+
+int vdb_ivf_filter_create_device(vdb_ivf* h, const uint64_t* d_filter_ids, uint64_t n_filter, int mode,
+                                 vdb_filter** out) {
+    return filter_create_entry(h, d_filter_ids, n_filter, mode, out, true);
+}
+
+int vdb_filter_combine(const vdb_filter* a, const vdb_filter* b, int op, vdb_filter** out) {
+    return guarded([&] {
+        require(a && b && out, "null argument");
+        require(a->h == b->h, "the two filters belong to different handles");
+        require(op == VDB_FILTER_AND || op == VDB_FILTER_OR || op == VDB_FILTER_ANDNOT, "invalid filter operation");
+        // (the handle is read, and its lock taken, only once the epoch says it still exists)
+        require(filter_epochs().live(a->h, a->epoch) && filter_epochs().live(b->h, b->epoch),
+                "the filter is stale: the handle's rows changed after it was prepared (prepare it again)", VDB_ERR_STATE);
+        std::lock_guard<std::mutex> g(a->h->mu);
+        a->h->set_device();
+        *out = filter_combine(*a, *b, op).release();
+    });
+}
+
+uint64_t vdb_filter_allowed(const vdb_filter* f) { return f ? f->n_allowed : 0; }
+
+int vdb_filter_stale(const vdb_filter* f) {
+    if (!f || !filter_epochs().live(f->h, f->epoch)) return 1;
+    std::lock_guard<std::mutex> g(f->h->mu);
+    return filter_live(*f) ? 0 : 1;
+}
+
+void vdb_filter_free(vdb_filter* f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    delete f;
+}
+
+int vdb_ivf_search_prepared(vdb_ivf* h, const vdb_filter* f, const float* q, uint32_t n, uint32_t nprobe, uint32_t k,
+                            float* dist, uint64_t* ids) {
+    return guarded([&] {
+        require(h && f && ((q && dist && ids) || n == 0 || k == 0), "null argument");  // (before any device call)
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        search_prepared(*h, *f, q, n, nprobe, k, dist, ids);
+    });
+}
+
+int vdb_ivf_range_search_prepared(vdb_ivf* h, const vdb_filter* f, const float* q, uint32_t n, uint32_t nprobe,
+                                  float radius, uint64_t reserve, vdb_range_result** out) {
+    return guarded([&] {
+        require(h && (q || n == 0) && out, "null argument");  // (a null filter: the unfiltered call)
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        *out = (f ? range_search_prepared(*h, *f, q, n, nprobe, radius, reserve)
+                  : range_search(*h, q, n, nprobe, radius, reserve))
+                   .release();
+    });
+}
+
+int vdb_filter_create_last_timing(double* sort_ms, double* mark_ms) {
+    if (sort_ms) *sort_ms = g_filter_create_timing.sort_ms;
+    if (mark_ms) *mark_ms = g_filter_create_timing.mark_ms;
+    return VDB_OK;
+}
+
 int vdb_ivf_search_device(vdb_ivf* h, const float* d_q, uint32_t n, uint32_t nprobe, uint32_t k, float* d_dist,
                           uint64_t* d_ids, void* stream) {
     return guarded([&] {
@@ -477,6 +578,7 @@ int vdb_ivf_set_shard(vdb_ivf* h, uint32_t rank, uint32_t world) {
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         no_group(h, "set_shard");
+        rows_may_move(h);
         h->set_shard(rank, world);
     });
 }
@@ -586,6 +688,7 @@ int vdb_ivf_set_shard_owners(vdb_ivf* h, uint32_t rank, uint32_t world, const ui
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         no_group(h, "set_shard");
+        rows_may_move(h);
         h->set_shard(rank, world, owner);
     });
 }
@@ -597,6 +700,7 @@ int vdb_ivf_plan_shard_owners(vdb_ivf* h, uint32_t rank, uint32_t world, const u
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         no_group(h, "plan_shard");
+        rows_may_move(h);
         h->plan_shard(rank, world, final_sizes, owner);
     });
 }
@@ -825,12 +929,14 @@ int vdb_ivf_set_option(vdb_ivf* h, const char* name, int64_t value) {
         } else if (n == "list_cache_bytes") {
             require(value >= 0, "list_cache_bytes out of range");
             h->set_device();
+            rows_may_move(h);
             h->set_list_cache((uint64_t)value);
             h->max_gpu_memory = 0;  // explicit residency control replaces the Config cap
             h->tier_by_cap = false;
         } else if (n == "max_gpu_memory") {
             require(value >= 0, "max_gpu_memory out of range");
             h->set_device();
+            rows_may_move(h);
             h->max_gpu_memory = (uint64_t)value;
             h->apply_memory_cap(h->count);  // (on, or back off when the tier came from the cap)
         } else if (n == "bounded_stats") {
@@ -945,6 +1051,7 @@ int vdb_ivf_open_lists(vdb_ivf* h, const char* path) {
         std::lock_guard<std::mutex> g(h->mu);
         no_group(h, "open_lists");
         h->set_device();
+        rows_may_move(h);
         h->open_lists(path);
     });
 }

@@ -1,6 +1,7 @@
 // exact_call.hpp — the host preamble of the exact-scan calls beside the engine (filter.cpp,
-// range.cpp): what they refuse, the fp32 layout they read, their grouping buffers and the head
-// of their scan arguments. A host header over vdb_ivf's public members, for those two files only.
+// range.cpp, and prepared.cpp which calls into both): what they refuse, the fp32 layout they
+// read, their grouping buffers and the head of their scan arguments. A host header over
+// vdb_ivf's public members, for those files only.
 #pragma once
 
 #include <algorithm>

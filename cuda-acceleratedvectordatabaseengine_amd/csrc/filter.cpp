@@ -20,6 +20,10 @@
 // existing scan kernel. It calls nothing that changes the handle: no screen_update,
 // screen_release, ensure_arena or upload_directory; the workspace is the call's own. What it
 // shares with range.cpp (the refusals, the layout choice, the grouping buffers) is exact_call.hpp.
+//
+// Two parts: search_filtered takes the masks from the call's sorted ids, and search_masked runs
+// steps 3 to 6 over masks already on the device. vdb_ivf_search_prepared (prepared.cpp) calls
+// the second part alone with a prepared filter's masks.
 #include "filter.hpp"
 
 #include <algorithm>
@@ -84,23 +88,14 @@ void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t npro
     g_filter_timing = FilterTiming{};
     if (n == 0 || k == 0) return;
     const uint32_t P = exact_probes(h, nprobe);
-    const size_t nk = (size_t)n * k;
-    auto all_unfilled = [&] {
-        std::fill(distances, distances + nk, FLT_MAX);
-        std::fill(ids, ids + nk, ~0ull);
-    };
-    if (P == 0 || h.arena_blocks == 0 || h.total == 0) return all_unfilled();
+    if (P == 0 || h.arena_blocks == 0 || h.total == 0) return search_masked(h, queries, n, nprobe, k, nullptr, nullptr, distances, ids);
     (void)resident_lists(h);  // (refused before any device work)
 
     hipStream_t s = h.stream;
     const uint64_t nb = h.arena_blocks;
-    DevBuf<uint64_t> d_sorted, d_out_i, d_slot_i, d_part_i, d_carry_i;
+    DevBuf<uint64_t> d_sorted;
     DevBuf<uint32_t> d_valid, d_allowed;
-    ScanGroupBufs grp;
-    DevBuf<unsigned long long> d_allow, d_pairs;
-    DevBuf<float> d_q, d_out_d, d_slot_d, d_part_d, d_carry_d;
-    vdb_ivf::SearchSlot w;  // the call's own workspace, not one of the ring's
-    BatchTimer timer;
+    DevBuf<unsigned long long> d_allow;
     hipEvent_t mark_ev[2] = {nullptr, nullptr};
     struct MarkEvents {
         hipEvent_t* e;
@@ -111,15 +106,12 @@ void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t npro
     } mark_guard{mark_ev};
     for (auto& x : mark_ev) HIPCHECK(hipEventCreate(&x));
     const std::vector<uint32_t> valid = remove_block_valid(h.count, h.block_off, h.owned, nb);
-    unsigned long long pairs = 0;
     StreamFence fence{s};  // (declared last: the stream is idle before anything above goes)
 
     // 1. the filter and the per-block valid counts to the device
     if (!sorted.empty())
         HIPCHECK(hipMemcpyAsync(d_sorted.ensure(sorted.size()), sorted.data(), sorted.size() * 8, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(d_valid.ensure(nb), valid.data(), nb * 4, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(d_q.ensure((size_t)n * h.dim), queries, (size_t)n * h.dim * 4, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(d_pairs.ensure(1), 0, 8, s));
 
     // 2. mark: per block the allow mask, per list the allowed rows (no host round trip)
     HIPCHECK(hipEventRecord(mark_ev[0], s));
@@ -129,6 +121,43 @@ void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t npro
     vdbk::launch_filter_count(d_allow.p, h.d_block_off.p, h.d_count_local.p, h.nlist, d_allowed.ensure(h.nlist), s);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(mark_ev[1], s));
+
+    // 3. to 6. the scan over those masks (it synchronises the stream and resets the timing)
+    search_masked(h, queries, n, nprobe, k, d_allow.p, d_allowed.p, distances, ids);
+    float mark = 0.f;
+    HIPCHECK(hipEventElapsedTime(&mark, mark_ev[0], mark_ev[1]));
+    g_filter_timing.mark_ms = mark;
+}
+
+void search_masked(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe, uint32_t k,
+                   const unsigned long long* d_allow, const uint32_t* d_allowed, float* distances, uint64_t* ids,
+                   const char* call) {
+    require(k <= vdbk::kFilterMaxK, std::string(call) + " serves k <= 64", VDB_ERR_UNSUPPORTED);
+    require_resident_single(h, call);
+    g_filter_timing = FilterTiming{};
+    if (n == 0 || k == 0) return;
+    const uint32_t P = exact_probes(h, nprobe);
+    const size_t nk = (size_t)n * k;
+    auto all_unfilled = [&] {
+        std::fill(distances, distances + nk, FLT_MAX);
+        std::fill(ids, ids + nk, ~0ull);
+    };
+    if (P == 0 || h.arena_blocks == 0 || h.total == 0) return all_unfilled();
+    (void)resident_lists(h);  // (refused before any device work)
+    require(d_allow && d_allowed, std::string(call) + ": no masks", VDB_ERR_STATE);
+
+    hipStream_t s = h.stream;
+    DevBuf<uint64_t> d_out_i, d_slot_i, d_part_i, d_carry_i;
+    ScanGroupBufs grp;
+    DevBuf<unsigned long long> d_pairs;
+    DevBuf<float> d_q, d_out_d, d_slot_d, d_part_d, d_carry_d;
+    vdb_ivf::SearchSlot w;  // the call's own workspace, not one of the ring's
+    BatchTimer timer;
+    unsigned long long pairs = 0;
+    StreamFence fence{s};  // (declared last: the stream is idle before anything above goes)
+
+    HIPCHECK(hipMemcpyAsync(d_q.ensure((size_t)n * h.dim), queries, (size_t)n * h.dim * 4, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(d_pairs.ensure(1), 0, 8, s));
 
     // a list longer than kScanSegBlocks blocks is cut into segments (the longest list's: the cap)
     const uint32_t segs = vdbk::scan_seg_cap(h.count.data(), h.owned.data(), h.nlist);
@@ -155,25 +184,25 @@ void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t npro
         hipEvent_t* ev = timer.take();
         // 4. the masked exact scan: the pairs grouped by list, then one item per (list segment, 4 queries)
         HIPCHECK(hipEventRecord(ev[0], s));
-        vdbk::launch_scan_group(w.probes.p, B * P, d_allowed.p, h.d_count_local.p, h.nlist, segs, vdbk::kFilterGroup,
+        vdbk::launch_scan_group(w.probes.p, B * P, d_allowed, h.d_count_local.p, h.nlist, segs, vdbk::kFilterGroup,
                                 grp.cursor.p, grp.pair_start.p, grp.item_start.p, grp.inv.p, s);
         HIPCHECK(hipGetLastError());
         vdbk::FilterScanArgs a;
         fill_scan_list_args(a, h, w, grp, B, P, segs);
-        a.allow = d_allow.p;
+        a.allow = d_allow;
         a.k = k;
         a.part_d = segs > 1 ? d_part_d.p : d_slot_d.p;
         a.part_i = segs > 1 ? d_part_i.p : d_slot_i.p;
         vdbk::launch_filter_scan(h.metric, a, s);
         HIPCHECK(hipGetLastError());
         if (segs > 1) {
-            vdbk::launch_filter_fold(d_part_d.p, d_part_i.p, w.probes.p, d_allowed.p, h.d_count_local.p, B * P, segs, k,
+            vdbk::launch_filter_fold(d_part_d.p, d_part_i.p, w.probes.p, d_allowed, h.d_count_local.p, B * P, segs, k,
                                      d_slot_d.p, d_slot_i.p, s);
             HIPCHECK(hipGetLastError());
         }
         HIPCHECK(hipEventRecord(ev[1], s));
         // 5. the merge; the stale carry crosses the batches, so results never depend on `batch`
-        vdbk::launch_filter_merge(w.probes.p, d_allowed.p, d_slot_d.p, d_slot_i.p, d_carry_d.p, d_carry_i.p, B, P, k,
+        vdbk::launch_filter_merge(w.probes.p, d_allowed, d_slot_d.p, d_slot_i.p, d_carry_d.p, d_carry_i.p, B, P, k,
                                   h.stale, d_out_d.p + (size_t)b0 * k, d_out_i.p + (size_t)b0 * k, d_pairs.p, s);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipEventRecord(ev[2], s));
@@ -184,9 +213,6 @@ void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t npro
     HIPCHECK(hipStreamSynchronize(s));
     // 6. the step times
     timer.finish();
-    float mark = 0.f;
-    HIPCHECK(hipEventElapsedTime(&mark, mark_ev[0], mark_ev[1]));
-    g_filter_timing.mark_ms = mark;
     g_filter_timing.scan_ms = timer.scan_ms;
     g_filter_timing.merge_ms = timer.merge_ms;
     g_filter_timing.pairs_scanned = pairs;

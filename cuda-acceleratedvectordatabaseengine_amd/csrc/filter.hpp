@@ -25,4 +25,13 @@ extern thread_local FilterTiming g_filter_timing;
 void search_filtered(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe, uint32_t k,
                      const std::vector<uint64_t>& sorted, bool include, float* distances, uint64_t* ids);
 
+// The second part of search_filtered, for masks already on h's device: d_allow[b] bit i = slot i
+// of arena block b is allowed (no bit at or above the block's valid count), d_allowed[l] = the
+// allowed rows of list l. Same caller duties, same result, same refusals (named after `call`);
+// resets the calling thread's timing and fills its scan, merge and pairs (mark_ms stays 0).
+// The masks may be null only where no scan runs (an empty handle, nprobe == 0, n == 0, k == 0).
+void search_masked(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe, uint32_t k,
+                   const unsigned long long* d_allow, const uint32_t* d_allowed, float* distances, uint64_t* ids,
+                   const char* call = "search_filtered");
+
 }  // namespace vdbe

@@ -10,8 +10,9 @@ constexpr uint32_t kFilterMaxK = 64;   // one top-k register per lane (WaveTopK<
 constexpr uint32_t kFilterGroup = 4;   // queries that probe the same list share one read of it
 
 // allow[b] bit i = slot i of block b holds a row (i < valid[b]) that the filter lets through:
-// include == 0: its id is not one of sorted[0..n); include != 0: it is. sorted is ascending,
-// each id once. Reads the ids of slots below valid[b] only (8 bytes per slot).
+// include == 0: its id is not one of sorted[0..n); include != 0: it is. sorted is ascending
+// (the binary search finds an id that stands more than once just as well). Reads the ids of
+// slots below valid[b] only (8 bytes per slot).
 void launch_filter_mark(const uint64_t* arena_ids, const uint32_t* valid, uint64_t nblocks, const uint64_t* sorted,
                         uint32_t n, int include, unsigned long long* allow, hipStream_t s);
 

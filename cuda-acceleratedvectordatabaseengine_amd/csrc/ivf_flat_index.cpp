@@ -67,11 +67,10 @@ void IVFFlatIndex::search_filtered(const float* queries, uint32_t n_queries, con
        "search_filtered");
 }
 
-void IVFFlatIndex::range_search(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
-                                std::vector<uint64_t>& lims, std::vector<float>& distances,
-                                std::vector<uint64_t>& indices) {
-    vdb_range_result* r = nullptr;
-    ok(vdb_ivf_range_search(h_, queries, n_queries, nprobe, radius, 0, &r), "range_search");
+namespace {
+// The library's result into the caller's vectors, then released.
+void take_range_result(vdb_range_result* r, uint32_t n_queries, std::vector<uint64_t>& lims,
+                       std::vector<float>& distances, std::vector<uint64_t>& indices) {
     struct Free {
         vdb_range_result* r;
         ~Free() { vdb_range_result_free(r); }
@@ -81,6 +80,52 @@ void IVFFlatIndex::range_search(const float* queries, uint32_t n_queries, uint32
     lims.assign(l, l + n_queries + 1);
     distances.assign(vdb_range_result_distances(r), vdb_range_result_distances(r) + total);
     indices.assign(vdb_range_result_ids(r), vdb_range_result_ids(r) + total);
+}
+}  // namespace
+
+void IVFFlatIndex::range_search(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
+                                std::vector<uint64_t>& lims, std::vector<float>& distances,
+                                std::vector<uint64_t>& indices) {
+    vdb_range_result* r = nullptr;
+    ok(vdb_ivf_range_search(h_, queries, n_queries, nprobe, radius, 0, &r), "range_search");
+    take_range_result(r, n_queries, lims, distances, indices);
+}
+
+IVFFlatIndex::Filter::~Filter() { vdb_filter_free(f_); }
+
+IVFFlatIndex::Filter& IVFFlatIndex::Filter::operator=(Filter&& o) noexcept {
+    if (this != &o) {
+        vdb_filter_free(f_);
+        f_ = o.f_;
+        o.f_ = nullptr;
+    }
+    return *this;
+}
+
+uint64_t IVFFlatIndex::Filter::allowed() const { return vdb_filter_allowed(f_); }
+
+bool IVFFlatIndex::Filter::stale() const { return vdb_filter_stale(f_) != 0; }
+
+IVFFlatIndex::Filter IVFFlatIndex::prepare_filter(const uint64_t* ids, uint64_t n_ids, bool include) {
+    vdb_filter* f = nullptr;
+    ok(vdb_ivf_filter_create(h_, ids, n_ids, include ? VDB_FILTER_INCLUDE : VDB_FILTER_EXCLUDE, &f), "prepare_filter");
+    return Filter(f);
+}
+
+void IVFFlatIndex::search_prepared(const float* queries, uint32_t n_queries, const SearchParams& params,
+                                   const Filter& filter, float* distances, uint64_t* indices) {
+    ok(vdb_ivf_search_prepared(h_, filter.handle(), queries, n_queries, params.nprobe, params.k, distances, indices),
+       "search_prepared");
+}
+
+void IVFFlatIndex::range_search_prepared(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
+                                         const Filter& filter, std::vector<uint64_t>& lims,
+                                         std::vector<float>& distances, std::vector<uint64_t>& indices) {
+    if (!filter.handle()) throw std::invalid_argument("range_search_prepared: an empty Filter");
+    vdb_range_result* r = nullptr;
+    ok(vdb_ivf_range_search_prepared(h_, filter.handle(), queries, n_queries, nprobe, radius, 0, &r),
+       "range_search_prepared");
+    take_range_result(r, n_queries, lims, distances, indices);
 }
 
 void IVFFlatIndex::search_batch(const std::vector<float*>& queries, const std::vector<SearchParams>& params,

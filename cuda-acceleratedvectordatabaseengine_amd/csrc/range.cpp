@@ -17,6 +17,11 @@
 // moment: the interleaved arena, or the screen's row-major copy while the arena is dropped.
 // Exact scan only.
 //
+// With a prepared filter's masks (d_allow, d_allowed: prepared.cpp) the same call runs over the
+// allowed rows: the allowed counts gate the grouping, so a list without an allowed row gets no
+// item, and the masked scan (ivf_range_scan_masked) appends allowed rows only. Everything after
+// the scan is the same code.
+//
 // A free function over vdb_ivf's public members, as filter.cpp is and for the same reason. It
 // calls nothing that changes the handle: no screen_update, screen_release, ensure_arena or
 // upload_directory; the workspace is the call's own. What it shares with filter.cpp (the
@@ -79,7 +84,8 @@ struct HitBufs {
 }  // namespace
 
 std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe,
-                                               float radius, uint64_t reserve) {
+                                               float radius, uint64_t reserve, const unsigned long long* d_allow,
+                                               const uint32_t* d_allowed) {
     require(!std::isnan(radius), "the radius is NaN");
     require_resident_single(h, "range_search");
     g_range_timing = RangeTiming{};
@@ -120,14 +126,16 @@ std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries,
         HIPCHECK(hipGetLastError());
         // 2. the pairs grouped by list, one item per (list segment, 8 queries); empty lists get none
         HIPCHECK(hipEventRecord(ev.e[0], s));
-        vdbk::launch_scan_group(w.probes.p, B * P, h.d_count_local.p, h.d_count_local.p, h.nlist, segs,
+        vdbk::launch_scan_group(w.probes.p, B * P, d_allow ? d_allowed : h.d_count_local.p, h.d_count_local.p, h.nlist, segs,
                                 vdbk::kRangeGroup, grp.cursor.p, grp.pair_start.p, grp.item_start.p, grp.inv.p, s);
         HIPCHECK(hipGetLastError());
         // 3. the thresholded scan, once more if the hits did not fit
         unsigned long long ctrl[vdbk::kRangeCtrlWords] = {};
         for (int pass = 0;; ++pass) {
-            vdbk::RangeScanArgs a;
+            vdbk::RangeMaskedScanArgs a;  // (the unmasked scan takes its RangeScanArgs part)
             fill_scan_list_args(a, h, w, grp, B, P, segs);
+            a.allow = d_allow;
+            a.allowed = d_allowed;
             a.radius = radius;
             a.cap = hit.cap;
             a.hit_key = hit.key_a;
@@ -137,7 +145,8 @@ std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries,
                     VDB_ERR_STATE);
             if (pass) HIPCHECK(hipEventRecord(ev.e[0], s));
             HIPCHECK(hipMemsetAsync(d_ctrl.p, 0, sizeof(ctrl), s));
-            vdbk::launch_range_scan(h.metric, a, s);
+            if (d_allow) vdbk::launch_range_scan_masked(h.metric, a, s);
+            else vdbk::launch_range_scan(h.metric, a, s);
             HIPCHECK(hipGetLastError());
             HIPCHECK(hipEventRecord(ev.e[1], s));
             HIPCHECK(hipMemcpyAsync(ctrl, d_ctrl.p, sizeof(ctrl), hipMemcpyDeviceToHost, s));

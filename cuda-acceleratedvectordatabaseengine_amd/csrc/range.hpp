@@ -35,7 +35,12 @@ extern thread_local RangeTiming g_range_timing;
 // result's order. Reads the handle only, and has synchronised h.stream when it returns or
 // throws. Refuses what it does not serve (a NaN radius, a group, a shard, a file home, the
 // list-cache tier) before any device work.
+// d_allow / d_allowed (both or neither): a prepared filter's per-block allow masks and per-list
+// allowed counts on the handle's device. The result is then the one of a handle with the same
+// centroids and metric that stores only the allowed rows in their original order.
 std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe,
-                                               float radius, uint64_t reserve);
+                                               float radius, uint64_t reserve,
+                                               const unsigned long long* d_allow = nullptr,
+                                               const uint32_t* d_allowed = nullptr);
 
 }  // namespace vdbe

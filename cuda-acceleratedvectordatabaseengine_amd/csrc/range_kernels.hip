@@ -21,6 +21,12 @@
 //                     wave-aggregated: ballot, one atomic add of the popcount by one lane, the
 //                     base broadcast, each hit lane at base + mbcnt. Past the buffer's capacity
 //                     nothing is written and the cursor keeps counting.
+//   ivf_range_scan_masked  the same body over the rows a prepared filter allows (MASKED): the
+//                     block's 64-bit allow mask read wave-uniform through the scalar cache, a
+//                     zero mask skipping the block unread, row-major staging lanes loading
+//                     allowed rows only, a hit needing its lane's bit; the one thing asked for
+//                     ahead is the mask word of the wave's next block of the same item. A sibling kernel with its
+//                     own argument block: ivf_range_scan is instruction for instruction unchanged.
 //   range_dedup       after the sorts by (query, distance) and by id: the first entry of each
 //                     (id, query) run keeps its key (-0.0f folded onto +0.0f), the others get the
 //                     key of no query.
@@ -57,6 +63,21 @@ typedef const float4 __attribute__((address_space(4))) ConstF4;
 #else
 typedef const float4 ConstF4;  // (the host pass only parses the kernels)
 #endif
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const unsigned long long __attribute__((address_space(4))) ConstU64;
+#else
+typedef const unsigned long long ConstU64;
+#endif
+
+// The argument block of a scan: the masked kernels carry the filter's two arrays behind it.
+template <bool MASKED>
+struct RangeArgsOf {
+    typedef RangeScanArgs type;
+};
+template <>
+struct RangeArgsOf<true> {
+    typedef RangeMaskedScanArgs type;
+};
 
 constexpr int kC4 = (int)kRangeChunk4;
 // one tile per wave: 64 rows x kC4 float4, a row padded by one float4 (36 words: the 16 lanes
@@ -66,9 +87,15 @@ typedef float4 RangeTile[64][kC4 + 1];
 // Blocks b_lo + wave, + kWaves, ... < b_hi of the list at arena block `base` (cnt rows) against
 // the np <= NG queries of pairs inv[p0 ..): NG distance chains per lane, chains g >= np repeat
 // the last query and are dropped.
-template <int M, bool ROWS, int NG>
-__device__ __forceinline__ void range_scan_blocks(const RangeScanArgs& a, float4 (*tile)[kC4 + 1], uint32_t p0, int np,
-                                                  uint32_t b_lo, uint32_t b_hi, uint64_t base, uint32_t cnt) {
+// MASKED: the block's allow mask is one wave-uniform 64-bit word, read like the queries through
+// the constant address space into SGPRs (the masks were written before the launch). A zero
+// mask skips the block before any row byte is loaded. Row-major layout: a staging lane loads
+// its float4 of a row only if that row's bit is set, so a sparse filter reads the allowed rows'
+// bytes alone; the tile rows of the other slots hold zeros and belong to lanes that never hit.
+template <int M, bool ROWS, int NG, bool MASKED>
+__device__ __forceinline__ void range_scan_blocks(const typename RangeArgsOf<MASKED>::type& a,
+                                                  float4 (*tile)[kC4 + 1], uint32_t p0, int np, uint32_t b_lo,
+                                                  uint32_t b_hi, uint64_t base, uint32_t cnt) {
     constexpr int C4 = kC4;
     const int lane = lane_id();
     const uint32_t wave = wave_index();
@@ -85,9 +112,26 @@ __device__ __forceinline__ void range_scan_blocks(const RangeScanArgs& a, float4
         q4[g] = (ConstF4*)(a.q + (size_t)qi[g] * d4 * 4);
     }
 
+    // MASKED: the masks of this wave's blocks, the next one asked for while the current block is
+    // summed (8 bytes of the item's own blocks, never beyond b_hi), so no block waits for its mask
+    ConstU64* masks = nullptr;
+    unsigned long long allow_next = 0;
+    if constexpr (MASKED) {
+        const uint64_t base_u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+                                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+        masks = (ConstU64*)a.allow + base_u;
+        if (b_lo + wave < b_hi) allow_next = masks[b_lo + wave];
+    }
+
     for (uint32_t b = b_lo + wave; b < b_hi; b += kWaves) {
         const uint64_t gb = base + b;
         const uint32_t valid = min(64u, cnt - b * 64);
+        unsigned long long allow = ~0ull;
+        if constexpr (MASKED) {
+            allow = allow_next;
+            if (b + kWaves < b_hi) allow_next = masks[b + kWaves];
+            if (allow == 0) continue;  // (wave-uniform) no row byte of this block is read
+        }
         float acc[NG];
 #pragma unroll
         for (int g = 0; g < NG; ++g) acc[g] = 0.0f;
@@ -96,15 +140,30 @@ __device__ __forceinline__ void range_scan_blocks(const RangeScanArgs& a, float4
                 // lane l fetches float4 (l & 7) of rows (l >> 3) + 8 i of the chunk
                 const float4* __restrict__ src = a.lists + (gb * 64 + (uint64_t)(lane >> 3)) * d4 + (lane & 7);
                 float4 nx[8];
+                // MASKED: bit 8 i of `rows_on` = row (lane >> 3) + 8 i of the block is allowed
+                const unsigned long long rows_on = allow >> (lane >> 3);
 #pragma unroll
-                for (int i = 0; i < 8; ++i) nx[i] = load_nt(src + (size_t)i * 8 * d4);
+                for (int i = 0; i < 8; ++i) {
+                    if constexpr (MASKED) {
+                        nx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                        if ((rows_on >> (8 * i)) & 1ull) nx[i] = load_nt(src + (size_t)i * 8 * d4);
+                    } else {
+                        nx[i] = load_nt(src + (size_t)i * 8 * d4);
+                    }
+                }
                 for (uint32_t c = 0; c < d4; c += C4) {
                     wave_sync();  // (the previous chunk's reads are done)
 #pragma unroll
                     for (int i = 0; i < 8; ++i) tile[i * 8 + (lane >> 3)][lane & 7] = nx[i];
                     if (c + C4 < d4) {  // the block's next chunk, never beyond the block
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) nx[i] = load_nt(src + (size_t)i * 8 * d4 + c + C4);
+                        for (int i = 0; i < 8; ++i) {
+                            if constexpr (MASKED) {
+                                if ((rows_on >> (8 * i)) & 1ull) nx[i] = load_nt(src + (size_t)i * 8 * d4 + c + C4);
+                            } else {
+                                nx[i] = load_nt(src + (size_t)i * 8 * d4 + c + C4);
+                            }
+                        }
                     }
                     wave_sync();
 #pragma unroll
@@ -130,7 +189,8 @@ __device__ __forceinline__ void range_scan_blocks(const RangeScanArgs& a, float4
         for (int g = 0; g < NG; ++g) {
             if (g < np) {  // (wave-uniform)
                 const float dv = dist_finish<M>(acc[g]);
-                const bool hit = (uint32_t)lane < valid && dv <= a.radius;  // (false for a NaN distance)
+                bool hit = (uint32_t)lane < valid && dv <= a.radius;  // (false for a NaN distance)
+                if constexpr (MASKED) hit = hit && ((allow >> lane) & 1ull);
                 const unsigned long long m = __ballot(hit);
                 if (m) {  // (wave-uniform)
                     if (hit && !have_id) {
@@ -151,8 +211,8 @@ __device__ __forceinline__ void range_scan_blocks(const RangeScanArgs& a, float4
     }
 }
 
-template <int M, bool ROWS>
-__global__ __launch_bounds__(kWaves * 64) void ivf_range_scan(const RangeScanArgs a) {
+template <int M, bool ROWS, bool MASKED>
+__device__ __forceinline__ void range_scan_body(const typename RangeArgsOf<MASKED>::type& a) {
     constexpr int G = (int)kRangeGroup;
     constexpr int C4 = kC4;
     __shared__ RangeTile s_x[ROWS ? kWaves : 1];
@@ -176,12 +236,28 @@ __global__ __launch_bounds__(kWaves * 64) void ivf_range_scan(const RangeScanArg
         const int np = (int)it.np;  // >= 1; slots g >= np repeat the last query
         const uint32_t cnt = a.count[it.list];
         const uint64_t base = a.block_off[it.list];
-        if (it.seg == 0 && threadIdx.x == 0) atomicAdd(a.ctrl + kRangePairs, (unsigned long long)np * cnt);
+        if constexpr (MASKED) {
+            if (it.seg == 0 && threadIdx.x == 0)
+                atomicAdd(a.ctrl + kRangePairs, (unsigned long long)np * a.allowed[it.list]);
+        } else {
+            if (it.seg == 0 && threadIdx.x == 0) atomicAdd(a.ctrl + kRangePairs, (unsigned long long)np * cnt);
+        }
         // (half the chains for a short group: a list few of the batch's queries probe)
         if (np <= G / 2)
-            range_scan_blocks<M, ROWS, G / 2>(a, s_x[ROWS ? wave : 0], it.p0, np, it.b_lo, it.b_hi, base, cnt);
-        else range_scan_blocks<M, ROWS, G>(a, s_x[ROWS ? wave : 0], it.p0, np, it.b_lo, it.b_hi, base, cnt);
+            range_scan_blocks<M, ROWS, G / 2, MASKED>(a, s_x[ROWS ? wave : 0], it.p0, np, it.b_lo, it.b_hi, base, cnt);
+        else range_scan_blocks<M, ROWS, G, MASKED>(a, s_x[ROWS ? wave : 0], it.p0, np, it.b_lo, it.b_hi, base, cnt);
     }
+}
+
+template <int M, bool ROWS>
+__global__ __launch_bounds__(kWaves * 64) void ivf_range_scan(const RangeScanArgs a) {
+    range_scan_body<M, ROWS, false>(a);
+}
+
+// The scan of vdb_ivf_range_search_prepared: a sibling kernel, so ivf_range_scan stays as it is.
+template <int M, bool ROWS>
+__global__ __launch_bounds__(kWaves * 64) void ivf_range_scan_masked(const RangeMaskedScanArgs a) {
+    range_scan_body<M, ROWS, true>(a);
 }
 
 // -0.0f and +0.0f are one key (key_less compares them equal; the id breaks the tie).
@@ -228,6 +304,13 @@ void scan_metric(const RangeScanArgs& a, hipStream_t s) {
     else ivf_range_scan<M, false><<<grid, kWaves * 64, 0, s>>>(a);
 }
 
+template <int M>
+void scan_metric_masked(const RangeMaskedScanArgs& a, hipStream_t s) {
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)a.B * a.P * a.segs, 256 * (a.rows ? 4 : 8));
+    if (a.rows) ivf_range_scan_masked<M, true><<<grid, kWaves * 64, 0, s>>>(a);
+    else ivf_range_scan_masked<M, false><<<grid, kWaves * 64, 0, s>>>(a);
+}
+
 // Key bits of a batch of B queries: the distance's 32 and enough for the query values 0 .. B.
 int key_bits(uint32_t B) {
     int qb = 1;
@@ -242,6 +325,13 @@ void launch_range_scan(int metric, const RangeScanArgs& a, hipStream_t s) {
     if (metric == kL2) scan_metric<kL2>(a, s);
     else if (metric == kIP) scan_metric<kIP>(a, s);
     else scan_metric<kCos>(a, s);
+}
+
+void launch_range_scan_masked(int metric, const RangeMaskedScanArgs& a, hipStream_t s) {
+    if (!a.B || !a.P) return;
+    if (metric == kL2) scan_metric_masked<kL2>(a, s);
+    else if (metric == kIP) scan_metric_masked<kIP>(a, s);
+    else scan_metric_masked<kCos>(a, s);
 }
 
 hipError_t range_order_temp_bytes(uint64_t m, uint32_t B, size_t& bytes) {

@@ -31,6 +31,18 @@ inline bool range_scan_serves(const RangeScanArgs& a) { return a.d4 > 0 && a.d4 
 // ctrl[kRangePairs] grows by the (query, row) distances computed.
 void launch_range_scan(int metric, const RangeScanArgs& a, hipStream_t s);
 
+// The same scan over the rows a filter allows (vdb_ivf_range_search_prepared). The unmasked
+// kernels keep their own argument block, so nothing of them changes.
+struct RangeMaskedScanArgs : RangeScanArgs {
+    const unsigned long long* allow = nullptr;  // per arena block: bit i = slot i is allowed (none at or above the block's valid count)
+    const uint32_t* allowed = nullptr;          // per list: its allowed rows (the popcounts of its blocks)
+};
+// Items of launch_scan_group with gate = `allowed`, so a list without an allowed row has none.
+// A block whose mask is zero is skipped before any row byte is loaded; in the row-major layout
+// only allowed rows are loaded. A hit is a slot below the valid count whose bit is set and
+// whose d <= radius. ctrl[kRangePairs] grows by the distances of allowed rows only.
+void launch_range_scan_masked(int metric, const RangeMaskedScanArgs& a, hipStream_t s);
+
 // The buffers that order m appended hits (each of at least m entries).
 struct RangeOrderBufs {
     uint64_t* key_a = nullptr;  // in: the scan's hit_key

@@ -18,6 +18,7 @@
 #include "vdb/transfer_manager.h"
 
 struct vdb_ivf;
+struct vdb_filter;
 
 namespace vdb {
 
@@ -65,6 +66,35 @@ public:
     // d <= radius, however many there are.
     void range_search(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
                       std::vector<uint64_t>& lims, std::vector<float>& distances, std::vector<uint64_t>& indices);
+    // Not in the reference: an id filter prepared once (vdb_ivf_filter_create) and kept on the
+    // device for any number of search_prepared / range_search_prepared calls. It owns its
+    // vdb_filter and may outlive the index; it is stale() once the index's rows changed (add,
+    // a remove that removed, load) or the index is gone, and a stale filter is refused.
+    class Filter {
+    public:
+        Filter() = default;
+        explicit Filter(vdb_filter* f) : f_(f) {}
+        ~Filter();
+        Filter(Filter&& o) noexcept : f_(o.f_) { o.f_ = nullptr; }
+        Filter& operator=(Filter&& o) noexcept;
+        Filter(const Filter&) = delete;
+        Filter& operator=(const Filter&) = delete;
+        uint64_t allowed() const;  // stored rows it lets through
+        bool stale() const;
+        vdb_filter* handle() const { return f_; }
+
+    private:
+        vdb_filter* f_ = nullptr;
+    };
+    // include: only rows whose id is listed are allowed; else every row whose id is not.
+    Filter prepare_filter(const uint64_t* ids, uint64_t n_ids, bool include);
+    // search_filtered's result for the filter's id set, without taking the masks again.
+    void search_prepared(const float* queries, uint32_t n_queries, const SearchParams& params, const Filter& filter,
+                         float* distances, uint64_t* indices);
+    // range_search on an index holding only the rows the filter allows.
+    void range_search_prepared(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
+                               const Filter& filter, std::vector<uint64_t>& lims, std::vector<float>& distances,
+                               std::vector<uint64_t>& indices);
     // Declared but never defined in the reference: here request i searches the single
     // query queries[i] with params[i] into distances[i] / indices[i] (params[i].k slots).
     void search_batch(const std::vector<float*>& queries, const std::vector<SearchParams>& params,

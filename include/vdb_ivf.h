@@ -182,8 +182,9 @@ int vdb_remove_last_timing(double* mark_ms, double* plan_ms, double* compact_ms,
  * give VDB_ERR_UNSUPPORTED; an invalid mode or a null buffer VDB_ERR_INVALID_ARGUMENT; a handle
  * in the list-cache tier (option list_cache_bytes, or max_gpu_memory exceeded), a file-home
  * handle (vdb_ivf_open_lists), a sharded handle (world > 1) and a group handle give
- * VDB_ERR_UNSUPPORTED. Not offered yet: a prepared, reusable filter object, a device-pointer
- * variant, the gRPC service, coalescing of concurrent filtered calls. */
+ * VDB_ERR_UNSUPPORTED. A filter many calls share is prepared once with vdb_ivf_filter_create
+ * (below), which also takes the ids from the device. Not offered yet: the gRPC service,
+ * coalescing of concurrent filtered calls. */
 enum { VDB_FILTER_EXCLUDE = 0, VDB_FILTER_INCLUDE = 1 };
 int vdb_ivf_search_filtered(vdb_ivf* index, const float* queries, uint32_t n, uint32_t nprobe, uint32_t k,
                             const uint64_t* filter_ids, uint64_t n_filter, int mode,
@@ -219,9 +220,9 @@ int vdb_filter_last_timing(double* mark_ms, double* scan_ms, double* merge_ms, u
  * Limits of this version (the handle is untouched by a refusal): a null handle, queries or out
  * and a NaN radius give VDB_ERR_INVALID_ARGUMENT; a handle in the list-cache tier, a file-home
  * handle, a sharded handle and a group handle give VDB_ERR_UNSUPPORTED, as does a batch with
- * more than 2^31 - 1 hits (lower the `batch` option). Not offered yet: a screened range scan,
- * per-query radii, a device-pointer variant, a filter combined with a radius, the gRPC service,
- * coalescing of concurrent range calls. */
+ * more than 2^31 - 1 hits (lower the `batch` option). A filter combined with a radius is
+ * vdb_ivf_range_search_prepared (below). Not offered yet: a screened range scan, per-query
+ * radii, a device-pointer variant, the gRPC service, coalescing of concurrent range calls. */
 typedef struct vdb_range_result vdb_range_result;
 int vdb_ivf_range_search(vdb_ivf* index, const float* queries, uint32_t n, uint32_t nprobe, float radius,
                          uint64_t reserve, vdb_range_result** out);
@@ -236,6 +237,56 @@ void vdb_range_result_free(vdb_range_result* r);                       /* NULL i
  * and the batches run again. Any pointer may be NULL; a thread without a call reads zeros. */
 int vdb_range_last_timing(double* scan_ms, double* order_ms, uint64_t* pairs_scanned, uint64_t* hits,
                           uint32_t* reruns);
+/* Prepared filters: the allow masks vdb_ivf_search_filtered takes from its ids on every call,
+ * taken once and kept on the device (8 bytes per 64 stored rows and 4 per list, nothing else)
+ * for any number of searches and range searches: a tombstone set, a tenant's ids, an ACL.
+ * vdb_ivf_filter_create takes a host array, vdb_ivf_filter_create_device an array on the
+ * handle's device that is complete before the call; mode, order, repeats, ids that are not
+ * stored, n_filter == 0 and the pad slots are as for vdb_ivf_search_filtered. The ids are sorted
+ * on the device, so a large set costs no host sort. *out is written on success only. Refused
+ * as vdb_ivf_search_filtered refuses: a null handle, ids or out and an invalid mode
+ * VDB_ERR_INVALID_ARGUMENT; n_filter >= 2^31, the list-cache tier, a file-home, a sharded and a
+ * group handle VDB_ERR_UNSUPPORTED.
+ * vdb_filter_combine makes a third filter of two live filters of one handle: VDB_FILTER_AND
+ * allows the rows both allow, VDB_FILTER_OR the rows either allows, VDB_FILTER_ANDNOT the rows
+ * a allows and b does not. (No bare NOT: no mask ever has a bit in a pad slot.) Filters of two
+ * handles give VDB_ERR_INVALID_ARGUMENT.
+ * A filter describes the handle's rows where they lay when it was made. It stays valid across
+ * searches of every kind, including the switch between the lists' two fp32 layouts; it is stale
+ * once a call has run that can move a row: vdb_ivf_add*, a vdb_ivf_remove_ids that removed a
+ * row, vdb_ivf_load, vdb_ivf_open_lists, vdb_ivf_set_shard* / vdb_ivf_plan_shard*,
+ * vdb_ivf_set_option of list_cache_bytes or max_gpu_memory, and vdb_ivf_destroy. A stale filter
+ * is refused with VDB_ERR_STATE by every call that takes one; vdb_filter_stale tells (1 also for
+ * NULL), and vdb_filter_free releases it, before or after the handle was destroyed.
+ * vdb_ivf_search_prepared returns, bit for bit, what vdb_ivf_search_filtered returns for the id
+ * set the filter was made from (for a combined filter: for the row set it allows), with the
+ * same limits (k <= 64); vdb_filter_last_timing reports it with mark_ms = 0.
+ * vdb_ivf_range_search_prepared returns the result of vdb_ivf_range_search on a handle with the
+ * same centroids and metric that stores only the allowed rows in their original order; all
+ * else (the inclusive comparison, ids stored twice, the order, reserve and the re-run, the
+ * independence of stale_slots and batch) as described there. filter == NULL is
+ * vdb_ivf_range_search. vdb_range_last_timing reports it; pairs_scanned counts the distances
+ * of allowed rows only. A block of 64 slots without an allowed row is skipped unread, and while
+ * the lists are held row-major only the allowed rows' bytes are read.
+ * A filter of another handle gives VDB_ERR_INVALID_ARGUMENT; what the one-shot calls refuse is
+ * refused the same way; a refusal leaves the handle untouched. Every call here holds the
+ * handle's lock and has finished its device work when it returns. */
+typedef struct vdb_filter vdb_filter;
+enum { VDB_FILTER_AND = 0, VDB_FILTER_OR = 1, VDB_FILTER_ANDNOT = 2 };
+int vdb_ivf_filter_create(vdb_ivf* index, const uint64_t* filter_ids, uint64_t n_filter, int mode, vdb_filter** out);
+int vdb_ivf_filter_create_device(vdb_ivf* index, const uint64_t* d_filter_ids, uint64_t n_filter, int mode,
+                                 vdb_filter** out);
+int vdb_filter_combine(const vdb_filter* a, const vdb_filter* b, int op, vdb_filter** out);
+uint64_t vdb_filter_allowed(const vdb_filter* filter);   /* stored rows it lets through */
+int vdb_filter_stale(const vdb_filter* filter);          /* 1 once the handle's rows changed or the handle is gone */
+void vdb_filter_free(vdb_filter* filter);                /* NULL is fine; valid after the handle was destroyed */
+int vdb_ivf_search_prepared(vdb_ivf* index, const vdb_filter* filter, const float* queries, uint32_t n,
+                            uint32_t nprobe, uint32_t k, float* distances, uint64_t* ids);
+int vdb_ivf_range_search_prepared(vdb_ivf* index, const vdb_filter* filter, const float* queries, uint32_t n,
+                                  uint32_t nprobe, float radius, uint64_t reserve, vdb_range_result** out);
+/* Diagnostics: the calling thread's latest vdb_ivf_filter_create(_device) (HIP events): the
+ * device sort of the ids, and the mark and count kernels. Either pointer may be NULL. */
+int vdb_filter_create_last_timing(double* sort_ms, double* mark_ms);
 /* Persist / restore centroids and lists (IVFFlatIndex::save/load, engine/ivf_flat_index.h:66-67,
  * declared but never defined in the reference; this engine's own file format). */
 int vdb_ivf_save(vdb_ivf* index, const char* path);

@@ -8,6 +8,10 @@ included, as for vdb_ivf_search):
   filtered  vdb_ivf_search_filtered at EXCLUDE 0 %, EXCLUDE 1 %, EXCLUDE 50 % and INCLUDE 1 % of
             the stored ids (random), with its mark / scan / merge split (HIP events) and the
             (query, row) distances it computed (pairs_scanned)
+  create    vdb_ivf_filter_create and vdb_ivf_filter_create_device for the 1 % and the 50 % id
+            sets: wall time of the call with its device sort / mark split (HIP events)
+  prepared  vdb_ivf_search_prepared with a filter prepared once from the same id sets, beside
+            the one-shot call of the same set in the same run
 The filtered calls run in both list layouts a handle can hold: the interleaved arena (screen =
 0) and the screen's row-major copy (screen = 1, after a plain search). Each figure is the
 median of `--repeats` calls after one warm-up call. Prints one JSON line per leg.
@@ -115,10 +119,53 @@ def main():
                       "mark_ms": med([x["mark_ms"] for x in steps]), "scan_ms": med([x["scan_ms"] for x in steps]),
                       "merge_ms": med([x["merge_ms"] for x in steps]), "pairs_scanned": steps[-1]["pairs_scanned"]})
 
+        def create(layout):
+            for name, f, inc in filters[1:3]:  # the 1 % and the 50 % sets
+                fd = torch.from_numpy(f.view(np.int64)).to(dev)
+                torch.cuda.synchronize()
+                for src in ("host", "device"):
+                    def call():
+                        if src == "host":
+                            return idx.prepare_filter(f, include=inc)
+                        return idx.prepare_filter(None, include=inc, device_ptr=fd.data_ptr(), n=len(f))
+                    call().close()
+                    t, steps = [], []
+                    for _ in range(args.repeats):
+                        t0 = time.perf_counter()
+                        flt = call()
+                        t.append((time.perf_counter() - t0) * 1e3)
+                        steps.append(idx.filter_create_last_timing())
+                        allowed = flt.allowed
+                        flt.close()
+                    emit({"what": "create", "layout": layout, "filter": name, "ids_from": src, "n_filter": int(len(f)),
+                          "wall_ms": med(t), "min": round(min(t), 3), "max": round(max(t), 3),
+                          "sort_ms": med([x["sort_ms"] for x in steps]), "mark_ms": med([x["mark_ms"] for x in steps]),
+                          "allowed": allowed})
+
+        def prepared(layout):
+            for name, f, inc in filters:
+                flt = idx.prepare_filter(f, include=inc)
+                idx.search_prepared(q, flt, nprobe=args.nprobe, k=args.k)
+                t, steps = [], []
+                for _ in range(args.repeats):
+                    t0 = time.perf_counter()
+                    idx.search_prepared(q, flt, nprobe=args.nprobe, k=args.k)
+                    t.append((time.perf_counter() - t0) * 1e3)
+                    steps.append(idx.filter_last_timing())
+                emit({"what": "prepared", "layout": layout, "filter": name, "n_filter": int(len(f)),
+                      "wall_ms": med(t), "min": round(min(t), 3), "max": round(max(t), 3),
+                      "scan_ms": med([x["scan_ms"] for x in steps]), "merge_ms": med([x["merge_ms"] for x in steps]),
+                      "pairs_scanned": steps[-1]["pairs_scanned"], "allowed": flt.allowed})
+                flt.close()
+
         plain(0)
         filtered("interleaved")
+        prepared("interleaved")
+        create("interleaved")
         plain(1)
         filtered("row-major")
+        prepared("row-major")
+        create("row-major")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:

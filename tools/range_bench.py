@@ -12,6 +12,11 @@ and the copy of the result included):
           events), the (query, row) distances computed, the entries returned, the batches run
           again, and the scan's read rate on 4 * dp * pairs_scanned / group bytes (group: the
           queries that share one read of a list, from the probes recomputed on the host)
+  masked  vdb_ivf_range_search_prepared at the first two radii under EXCLUDE nothing, EXCLUDE
+          50 % and INCLUDE 1 % of the stored ids (random, prepared once), with the bytes of list
+          rows the masked scan reads: per list cdiv(pairs, group) reads of, in the interleaved
+          layout, every 64-slot block with an allowed row, and in the row-major layout of the
+          allowed rows alone (the masks recomputed on the host from the lists' ids)
 The range calls run in both list layouts a handle can hold: the interleaved arena (screen = 0)
 and the screen's row-major copy (screen = 1, after a plain search). Each figure is the median of
 `--repeats` calls after one warm-up call, with min and max. Prints one JSON line per leg.
@@ -120,6 +125,57 @@ def main():
         emit({"what": "reads", "pairs_host": int((per_list * sizes).sum()), "rows_read": rows_read,
               "group": round(float((per_list * sizes).sum()) / max(rows_read, 1), 3), "read_bytes": rows_read * dp * 4})
 
+        # the filters, and per list what a masked scan reads of it
+        rng = np.random.default_rng(7)
+        one = rng.choice(n, size=max(1, n // 100), replace=False).astype(np.uint64)
+        half = rng.choice(n, size=n // 2, replace=False).astype(np.uint64)
+        filters = [("exclude_0pct", np.empty(0, np.uint64), False), ("exclude_50pct", half, False),
+                   ("include_1pct", one, True)]
+        list_ids = []
+        buf_v = np.empty((int(sizes.max()), dim), dtype=np.float32)
+        for l in range(args.nlist):
+            li = np.empty(int(sizes[l]), dtype=np.uint64)
+            if sizes[l]:
+                idx.get_list_into(l, buf_v[:int(sizes[l])], li)
+            list_ids.append(li)
+        del buf_v
+        reads = -(-per_list // GROUP)
+
+        def masked_bytes(f, inc):
+            listed = np.zeros(n, dtype=bool)
+            listed[f.astype(np.int64)] = True
+            il = rm = 0
+            for l in range(args.nlist):
+                allow = listed[list_ids[l].astype(np.int64)] == inc
+                pad = (-allow.size) % 64
+                blocks = np.concatenate([allow, np.zeros(pad, bool)]).reshape(-1, 64).any(axis=1)
+                il += int(reads[l]) * int(blocks.sum()) * 64
+                rm += int(reads[l]) * int(allow.sum())
+            return il * dp * 4, rm * dp * 4
+
+        def masked(layout):
+            for name, f, inc in filters:
+                flt = idx.prepare_filter(f, include=inc)
+                b_il, b_rm = masked_bytes(f, inc)
+                for rname, r in radii[:2]:
+                    idx.range_search_prepared(q, flt, r, nprobe=args.nprobe)
+                    t, steps = [], []
+                    for _ in range(args.repeats):
+                        t0 = time.perf_counter()
+                        idx.range_search_prepared(q, flt, r, nprobe=args.nprobe)
+                        t.append((time.perf_counter() - t0) * 1e3)
+                        steps.append(idx.range_last_timing())
+                    scan = med([x["scan_ms"] for x in steps])
+                    emit({"what": "masked_range", "layout": layout, "filter": name, "radius": rname, "r": r,
+                          "wall_ms": med(t), "min": round(min(t), 3), "max": round(max(t), 3), "scan_ms": scan,
+                          "scan_min": round(min(x["scan_ms"] for x in steps), 3),
+                          "scan_max": round(max(x["scan_ms"] for x in steps), 3),
+                          "order_ms": med([x["order_ms"] for x in steps]), "pairs_scanned": steps[-1]["pairs_scanned"],
+                          "hits": steps[-1]["hits"], "allowed": flt.allowed,
+                          "row_bytes": b_il if layout == "interleaved" else b_rm,
+                          "row_bytes_share": round((b_il if layout == "interleaved" else b_rm) / (rows_read * dp * 4), 4)})
+                flt.close()
+
         def ranged(layout):
             for name, r in radii:
                 idx.range_search(q, r, nprobe=args.nprobe)
@@ -133,14 +189,18 @@ def main():
                 passes = 1 + steps[-1]["reruns"]
                 emit({"what": "range", "layout": layout, "radius": name, "r": r, "wall_ms": med(t),
                       "min": round(min(t), 3), "max": round(max(t), 3), "scan_ms": scan,
+                      "scan_min": round(min(x["scan_ms"] for x in steps), 3),
+                      "scan_max": round(max(x["scan_ms"] for x in steps), 3),
                       "order_ms": med([x["order_ms"] for x in steps]), "pairs_scanned": steps[-1]["pairs_scanned"],
                       "hits": steps[-1]["hits"], "reruns": steps[-1]["reruns"],
                       "scan_TBps": round(rows_read * dp * 4 * passes / (scan * 1e-3) / 1e12, 3) if scan > 0 else None})
 
         plain(0)
         ranged("interleaved")
+        masked("interleaved")
         plain(1)
         ranged("row-major")
+        masked("row-major")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:
