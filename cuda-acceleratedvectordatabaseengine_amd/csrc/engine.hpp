@@ -43,6 +43,7 @@
 #include "floor.hpp"
 #include "list_cache.hpp"
 #include "row_reader.hpp"
+#include "scan_route.hpp"
 #include "uring.hpp"
 
 namespace vdbe {
@@ -331,11 +332,7 @@ struct vdb_ivf {
     int screen_i8 = 2;
     bool i8_vetoed = false;  // (automatic: the calibration vetoed int8 for this handle)
     uint32_t last_P = 0;     // the nprobe of the search that triggers a screen build
-    bool want_i8() const {
-        if (!screen_defer) return false;
-        if (screen_i8 != 2) return screen_i8 == 1;
-        return !tiered() && !i8_vetoed;
-    }
+    bool want_i8() const { return vdbe::want_i8(knobs(), facts()); }
     uint32_t screen_thr_every = 0;  // deferred collect: blocks between re-reads of the shared thresholds, 0 = automatic (option screen_thr_every)
     // Deferred re-checks (option screen_defer, default 1): the scan only collects candidates
     // against upper-bound thresholds; survivors of each pair's final threshold are re-checked
@@ -868,55 +865,18 @@ struct vdb_ivf {
     // Upload the list directory and recompute the segment-count prefix.
     void upload_directory() {
         quiesce();
-        // Segment size: the largest of 512/256/128/64 vectors that still cuts this
-        // handle's lists into >= 4096 segments, so a shard of an 8-GPU node keeps
-        // enough scan work items for load balance (measured on a 1/8 shard of the
-        // 10M x 768 index: 256 beats 512 by 5 % and 64 by 9 %).
-        uint64_t local = 0;
-        for (uint32_t l = 0; l < nlist; ++l) local += owned[l] ? count[l] : 0;
-        if (seg_blocks_opt) {
-            seg_blocks = seg_blocks_opt;
-        } else {
-            seg_blocks = 8;  // 512 vectors at most by default (1024 is an explicit option)
-            // (The screen keeps 512 at every shard size. 256-vector segments in items of 4 made
-            // the 1/8 shard's one-in-flight scan faster (0.549 vs 0.575 ms) but its batches at
-            // 3 in flight slower (0.47 vs 0.41 ms per step over the 8 emulated ranks: more
-            // items, partials and merge work per batch), so throughput keeps 512.)
-            const bool screen_may = screen_opt && metric != 2;
-            while (!screen_may && seg_blocks > 1 && local / ((uint64_t)seg_blocks * 64) < 4096) seg_blocks >>= 1;
-        }
-        std::vector<uint32_t> cl(nlist), cg(nlist), ns(nlist);
-        storable_n = 0;
-        for (uint32_t l = 0; l < nlist; ++l) {
-            require(count[l] < (1ull << 32), "list longer than 2^32 vectors", VDB_ERR_UNSUPPORTED);
-            cg[l] = (uint32_t)count[l];
-            cl[l] = owned[l] ? (uint32_t)count[l] : 0u;
-            storable_n += cl[l] > 0;
-            ns[l] = (uint32_t)cdiv(cl[l], (uint64_t)seg_blocks * 64);
-        }
+        // (segment size, counts, segment counts and the screened items' length: scan_route.hpp)
+        ScanDirectory dir = scan_directory(count, owned, seg_blocks_opt, screen_opt, metric);
+        require(dir.ok, "list longer than 2^32 vectors", VDB_ERR_UNSUPPORTED);
+        seg_blocks = dir.seg_blocks;
+        storable_n = dir.storable_n;
+        screen_segs_auto = dir.screen_segs_auto;
+        nseg_prefix = std::move(dir.nseg_prefix);
         upload_scan_directory(stream);
-        HIPCHECK(hipMemcpyAsync(d_count_local.ensure(nlist), cl.data(), nlist * 4, hipMemcpyHostToDevice, stream));
-        HIPCHECK(hipMemcpyAsync(d_count_global.ensure(nlist), cg.data(), nlist * 4, hipMemcpyHostToDevice, stream));
-        HIPCHECK(hipMemcpyAsync(d_nseg.ensure(nlist), ns.data(), nlist * 4, hipMemcpyHostToDevice, stream));
-        // Screened items: a wave carries its top-k across the segments it takes from one item,
-        // so items of long lists take more segments (its thresholds tighten over more
-        // vectors); short lists keep 4 for parallelism. By the size-weighted mean segment
-        // count of the stored lists (measured: iid 10M x 768, 40 per list: 8; the 1/8 shard
-        // of 100M x 768, ~200: 16; the mixture, 5: 4).
-        {
-            double wsum = 0.0, wseg = 0.0;
-            for (uint32_t l = 0; l < nlist; ++l) {
-                wsum += cl[l];
-                wseg += (double)cl[l] * ns[l];
-            }
-            const double mean_seg = wsum > 0 ? wseg / wsum : 0.0;
-            screen_segs_auto = mean_seg < 16.0 ? 4u : (mean_seg < 96.0 ? 8u : 16u);
-        }
-        std::vector<uint32_t> sorted(ns);
-        std::sort(sorted.begin(), sorted.end(), std::greater<uint32_t>());
-        nseg_prefix.assign(nlist + 1, 0);
-        for (uint32_t j = 0; j < nlist; ++j) nseg_prefix[j + 1] = nseg_prefix[j] + sorted[j];
-        HIPCHECK(hipStreamSynchronize(stream));  // host vectors above are stack-owned
+        HIPCHECK(hipMemcpyAsync(d_count_local.ensure(nlist), dir.count_local.data(), nlist * 4, hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipMemcpyAsync(d_count_global.ensure(nlist), dir.count_global.data(), nlist * 4, hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipMemcpyAsync(d_nseg.ensure(nlist), dir.nseg.data(), nlist * 4, hipMemcpyHostToDevice, stream));
+        HIPCHECK(hipStreamSynchronize(stream));  // (dir's vectors are stack-owned)
         screen_stale = true;  // rebuilt by the next search (a bulk add appends in many calls)
     }
 
@@ -2003,10 +1963,8 @@ struct vdb_ivf {
     // Size every per-batch buffer of a slot for B queries up front; growing a buffer
     // frees the old one, so first wait for the slot's previous batch.
     void ensure_workspace(SearchSlot& w, uint32_t B, uint32_t P, uint32_t k) {
-        const size_t BP = (size_t)B * P;
-        const size_t max_items = (size_t)B * nseg_prefix[P];
-        const size_t max_l1 = max_items / vdbk::kMergeFan + BP;
-        const size_t max_wide = max_items / 4 + BP + 1;
+        const ScanBounds bd = scan_bounds(kScanConsts, nseg_prefix, B, P);  // (what scan_batch launches by)
+        const size_t BP = bd.BP, max_items = bd.max_items, max_l1 = bd.max_l1, max_wide = bd.max_wide;
         const bool grow = w.items_w.cap < max_wide || w.qpad.cap < (size_t)B * dp || w.cd.cap < (size_t)B * nlist ||
                           w.cdelta.cap < (size_t)B * nlist || w.cand.cap < (size_t)B * nlist ||
                           w.probes.cap < BP || w.thr.cap < BP || w.items.cap < max_items || w.part_d.cap < max_items * k ||
@@ -2079,47 +2037,30 @@ struct vdb_ivf {
     // exact list-cache path instead (run_batch).
     bool scan_batch(SearchSlot& w, uint32_t B, uint32_t P, uint32_t k, float* out_d_, uint64_t* out_i_, hipStream_t s,
                     const uint32_t* req_start, uint32_t b0, EventSet* ev) {
-        const int regs_k = vdbk::topk_regs(k);
-        const uint32_t group = (uint32_t)vdbk::scan_group(regs_k);
-        const uint32_t BP = B * P;
-        const uint64_t max_items = (uint64_t)B * nseg_prefix[P];
-        require(max_items < (1ull << 32), "batch too large", VDB_ERR_UNSUPPORTED);
+        const ScanBounds bd = scan_bounds(kScanConsts, nseg_prefix, B, P);  // (what ensure_workspace sized by)
+        require(bd.ok(), "batch too large", VDB_ERR_UNSUPPORTED);
+        const uint32_t BP = (uint32_t)bd.BP;
         // (tier: lists and directory entries another stream loaded must have landed)
         if (tiered() && tier_ev_used) HIPCHECK(hipStreamWaitEvent(s, tier_ev, 0));
-        const uint64_t max_l1 = max_items / vdbk::kMergeFan + BP;
-        const uint64_t max_wide = max_items / 4 + BP + 1;
         last_P = P;
         if (screen_stale) screen_update();
-        // the screened scan (default, L2 / IP, k <= 64): items of swq queries
-        const uint32_t swq = screen_width(k, P);
-        bool screened = swq != 0 && !force_exact;
+        // The route (scan_route.hpp): screened (default, L2 / IP, k <= 64) in items of swq
+        // queries unless the run-time floor (lists in HBM only) sends the batch to the exact
+        // scan; then every size and grid of the launches below.
+        const ScanKnobs kn = knobs();
+        const ScanFacts fa = facts();
+        const ScanFits fit = fits(k);
+        const int regs_k = fit.regs_k;
+        const uint32_t swq = vdbe::screen_width(kn, fa, fit, P);
         uint32_t floor_seq = 0;
-        if (screened && !tiered() && screen_defer && !calibrating)  // the run-time floor (lists in HBM only)
-            screened = floor.plan([this](uint32_t i) { return floor_entry(i); }, &floor_seq);
-        // Exact scans on lists in HBM whose interleaved arena was released read the row-major
-        // copy (4-wave items); the opt-in bounded scan needs the interleaved layout back.
-        bool rows_l = !screened && arena_dropped && !tiered();
-        if (rows_l && scan_mfma_min && regs_k == 1 && wide_scan && metric != 2) {
-            ensure_arena();
-            rows_l = false;
-        }
-        const int waves = wide_group == 32 && !rows_l ? 8 : 4;  // workgroup shape of the wide scan
-        // (Cosine: every CPU-path distance is 0.0f, A5; its lists scan as narrow items only)
-        const bool wide = regs_k == 1 && wide_scan && metric != 2 && vdbk::scan_wide_fits(d4, k, waves);
-        // segments per item: one per wave (more adds tail latency, no throughput)
-        const uint32_t segs_item = segs_item_opt ? segs_item_opt : (uint32_t)waves;
-        // wide items of many queries: bounded on the matrix cores (L2 / IP, 16-query items)
-        const uint32_t mfma_min = !screened && !rows_l && wide && waves == 4 && metric != 2 && !(VDB_SCAN_DIAG & 2) &&
-                                          vdbk::scan_bounded_fits(d4, k)
-                                      ? scan_mfma_min : 0u;
-        const int plan_wide = screened ? (int)swq : (wide ? 4 * waves : 0);
-        // (screened items: segs_per_item segments, default 4; a wave's top-k carries across
-        // the segments it takes from one item)
-        const uint32_t segs_screen = segs_item_opt ? segs_item_opt : screen_segs_auto;
+        const bool floor_ok =
+            !floor_applies(kn, fa, swq) || floor.plan([this](uint32_t i) { return floor_entry(i); }, &floor_seq);
+        const ScanRoute r = scan_route(kScanConsts, kn, fa, fit, bd, swq, floor_ok);
+        if (r.need_arena) ensure_arena();
         auto plan = [&](unsigned long long* st) {
-            vdbk::launch_plan(w.probes.p, d_nseg.p, d_count_local.p, B, P, group, plan_wide, screened ? segs_screen : segs_item,
-                              w.items.p, w.items_w.p, w.counters.p, w.sorted_pair.p, w.pbs.p, w.pbqp.p, w.nseg_qp.p,
-                              w.l1base.p, w.l1_items.p, st, w.thr.p, mfma_min, s);
+            vdbk::launch_plan(w.probes.p, d_nseg.p, d_count_local.p, B, P, (uint32_t)vdbk::scan_group(regs_k), r.plan_wide,
+                              r.segs(), w.items.p, w.items_w.p, w.counters.p, w.sorted_pair.p, w.pbs.p, w.pbqp.p,
+                              w.nseg_qp.p, w.l1base.p, w.l1_items.p, st, w.thr.p, r.mfma_min, s);
         };
         // (the automatic shadow's calibration batch counts into scratch: profile_read reports
         // the caller's batches only)
@@ -2130,25 +2071,18 @@ struct vdb_ivf {
             if (prev.scan_done) HIPCHECK(hipStreamWaitEvent(s, prev.scan_done, 0));
         }
         if (ev) HIPCHECK(hipEventRecord(ev->scan_begin, s));
-        const float4* lists = tiered() ? cache.p : rows_l ? (const float4*)screen_rows.p : arena.p;
+        const float4* lists = tiered() ? cache.p : r.rows_l ? (const float4*)screen_rows.p : arena.p;
         vdbk::ScanArgs sa{lists, tiered() ? cache_ids.p : arena_ids.p, d_block_off.p, d_count_local.p, w.q, w.items.p, w.items_w.p,
                                 w.counters.p, w.sorted_pair.p, w.pbs.p, w.part_d.p, w.part_i.p, d4, k,
-                                wide_stride, w.counters.p + 4, seg_blocks, segs_item, 0, w.thr.p,
-                                mfma_min, bounded_stats && !calibrating ? stats.p + 5 : nullptr};
-        sa.rows_layout = rows_l ? 1u : 0u;
+                                wide_stride, w.counters.p + 4, seg_blocks, r.segs(), 0, w.thr.p,
+                                r.mfma_min, bounded_stats && !calibrating ? stats.p + 5 : nullptr};
+        sa.rows_layout = r.rows_l ? 1u : 0u;
         // the bounded items first (the batch's most-probed lists), on the same stream
-        if (mfma_min) vdbk::launch_scan_bounded(metric, (uint32_t)max_wide, sa, s);
-        if (screened) {
-            const bool defer = screen_defer;
-            const bool i8s = defer && screen_fmt_i8;  // (int8 shadow: built only for the deferred scan)
-            // (the tier's file home reads the survivors' rows on the host: the batch then
-            // waits for its selection, and re-runs with a larger buffer if it overflowed)
-            const bool tier_file = tiered() && file_home();
-            // candidates at most: every (query, vector) pair the batch can have (B queries x the
-            // P largest stored lists), capped by the option
-            uint32_t ccap = (uint32_t)std::min<uint64_t>(
-                screen_cand_cap, std::max<uint64_t>(1024, (uint64_t)B * nseg_prefix[P] * seg_blocks * 64));
-            if (tier_file) ccap = std::max(ccap, tier_cand_cap);
+        if (r.mfma_min) vdbk::launch_scan_bounded(metric, (uint32_t)bd.max_wide, sa, s);
+        if (r.screened) {
+            const bool defer = r.shape == ScanShape::ScreenDeferred;
+            const bool i8s = r.i8s, tier_file = r.tier_file;
+            uint32_t ccap = r.ccap;  // (an overflow re-run grows it)
             auto alloc_defer = [&]() {
                 slot_buf(w, w.scnt, BP);
                 slot_buf(w, w.ovf, BP);
@@ -2158,7 +2092,7 @@ struct vdb_ivf {
                 slot_buf(w, w.sdist, ccap);
                 slot_buf(w, w.ubcnt, BP);
                 slot_buf(w, w.ublist, (size_t)BP * vdbk::kUbLists * k);
-                if (tier_file && screen_recheck2) {
+                if (r.tier2) {
                     slot_buf(w, w.slb, ccap);
                     slot_buf(w, w.smark, ccap);
                     slot_buf(w, w.rowmap, ccap);
@@ -2183,30 +2117,18 @@ struct vdb_ivf {
             sa.pst = w.pst.p;
             sa.dp = dp;
             sa.P = P;
-            sa.segs_item = segs_screen;
-            sa.wide_q = swq;
-            // (32-query items run one workgroup per CU, so a shared-threshold read's latency is
-            // exposed: re-read every 4 blocks, cfg4 shard collect 4.14 -> 3.87 ms; 16-query
-            // items hide it and keep the freshest value, 1/8 shard 0.543 vs 0.552 ms)
-            sa.thr_every = screen_thr_every ? screen_thr_every : (swq == 32 ? 4u : 1u);
+            sa.wide_q = r.swq;
+            sa.thr_every = r.thr_every;
+            sa.fused = r.fused;
             if (tiered()) {  // the resident shadow's packing and ids; rows from the home
                 sa.block_off = d_sblock_off.p;
                 sa.ids = screen_ids.p;
                 sa.rows = nullptr;
                 sa.arena = file_home() ? nullptr : arena.p;  // (host home: page-locked, read over PCIe)
             }
-            sa.fused = std::max<uint32_t>(1, std::min<uint32_t>(narrow_blocks, vdbk::kPersistentBlocks / 2));
-            const uint64_t want = std::max<uint64_t>(max_wide, (max_items + 3) / 4);
-            // (the persistent collect grid of 16-query items: 320 workgroups, 1.25 per CU, not 2:
-            // the CU slots left over run the other batches in flight; measured on one box,
-            // 320 / 352 / 384 / 512: headline 28.5K / 28.2K / 28.1K / 27.4K QPS, mixture 53.6K /
-            // 53.9K / 54.0K / 52.0K, 1/8 shard at 3 in flight 184.5K / 182.7K / 181.8K / 174.4K)
-            const uint64_t cap = scan_blocks ? scan_blocks : (swq == 32 ? vdbk::kPersistentBlocks / 2 : kCollectBlocks);
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(want, cap);
             if (defer) {
                 const float* fetched = nullptr;
-                const bool recheck2 = screen_recheck2 && !tiered();  // (rows in HBM, by slot)
-                const bool tier2 = screen_recheck2 && tier_file;       // (rows from the file, two read phases)
+                const bool recheck2 = r.recheck2, tier2 = r.tier2;
                 for (int pass = 0;; ++pass) {
                     if (pass) {  // a re-run after an overflow (tier, file home): plan and pairs reset the state
                         alloc_defer();
@@ -2234,7 +2156,7 @@ struct vdb_ivf {
                         sa.stamp_batch = stamp_batch++;
                     }
                     if (ev) HIPCHECK(hipEventRecord(ev->collect_begin, s));
-                    vdbk::launch_screen_collect(metric, grid, sa, s);
+                    vdbk::launch_screen_collect(metric, r.grid_collect, sa, s);
                     if (ev) {
                         HIPCHECK(hipEventRecord(ev->collect_end, s));
                         ev->collected = true;
@@ -2282,27 +2204,20 @@ struct vdb_ivf {
                                                 recheck2 ? w.sdist.p : nullptr);
                 }
             } else {
-                vdbk::launch_scan_screen(metric, grid, sa, s);
+                vdbk::launch_scan_screen(metric, r.grid_collect, sa, s);
             }
-        } else if (wide && fused_scan) {
-            // one persistent grid takes both queues (no side stream, no fork/join)
-            // (narrow_blocks counts 4-wave workgroups: as many waves start on the narrow queue)
-            const uint32_t grid_cap = waves == 8 ? vdbk::kPersistentBlocks / 2 : vdbk::kPersistentBlocks;
-            sa.fused = std::max<uint32_t>(1, std::min<uint32_t>(narrow_blocks * 4 / waves, grid_cap / 2));
-            const uint64_t want = std::max<uint64_t>(max_wide, (max_items + 3) / 4);
-            vdbk::launch_scan_wide(metric, (uint32_t)(scan_blocks ? std::min<uint64_t>(want, scan_blocks) : want), sa, s,
-                                   waves);
-        } else if (wide) {
-            // narrow items on the side stream fill the CUs the wide items leave idle
+        } else if (r.shape == ScanShape::FusedWide) {
+            sa.fused = r.fused;
+            vdbk::launch_scan_wide(metric, r.grid_wide, sa, s, r.waves);
+        } else if (r.shape == ScanShape::WideSide) {
             HIPCHECK(hipEventRecord(w.fork, s));
             HIPCHECK(hipStreamWaitEvent(w.side, w.fork, 0));
-            vdbk::launch_scan_narrow(metric, regs_k, std::min<uint32_t>((uint32_t)((max_items + 3) / 4), narrow_blocks), sa,
-                                     w.side);
+            vdbk::launch_scan_narrow(metric, regs_k, r.grid_narrow, sa, w.side);
             HIPCHECK(hipEventRecord(w.join, w.side));
-            vdbk::launch_scan_wide(metric, (uint32_t)max_wide, sa, s, waves);
+            vdbk::launch_scan_wide(metric, r.grid_wide, sa, s, r.waves);
             HIPCHECK(hipStreamWaitEvent(s, w.join, 0));
         } else {
-            vdbk::launch_scan_narrow(metric, regs_k, (uint32_t)((max_items + 3) / 4), sa, s);
+            vdbk::launch_scan_narrow(metric, regs_k, r.grid_narrow, sa, s);
         }
         if (ev) HIPCHECK(hipEventRecord(ev->scan_end, s));
         if (scan_window && in_ring) {
@@ -2325,7 +2240,7 @@ struct vdb_ivf {
             HIPCHECK(hipGetLastError());
             return true;
         }
-        vdbk::launch_merge_partials(regs_k, (uint32_t)max_l1, w.probes.p, d_count_global.p, w.nseg_qp.p, w.pbqp.p, w.l1base.p,
+        vdbk::launch_merge_partials(regs_k, (uint32_t)bd.max_l1, w.probes.p, d_count_global.p, w.nseg_qp.p, w.pbqp.p, w.l1base.p,
                                     w.l1_items.p, w.counters.p, w.part_d.p, w.part_i.p, k, w.l1_d.p, w.l1_i.p, s);
         vdbk::launch_slot_merge(regs_k, w.probes.p, d_count_global.p, w.nseg_qp.p, w.pbqp.p, w.l1base.p, w.part_d.p, w.part_i.p,
                                 w.l1_d.p, w.l1_i.p, BP, k, w.slot_d.p, w.slot_i.p, s);
@@ -2464,43 +2379,58 @@ struct vdb_ivf {
         tier_call_used = true;
     }
 
-    // The screened scan's item width for a search (16 or 32 queries), or 0 when the screen
-    // does not serve it. ONE decision for scan_batch and for the tier's routing
-    // (screen_serves): a search the tier sends past its list cache is always screened.
-    // 32-query items (option screen_group; 0 = automatic: 32 from nprobe 64 up, where hub
-    // lists are probed by many queries of a batch: cfg4 shard collect 4.45 vs 4.69 ms; 16
-    // below: cfg3 2.54 vs 2.72 ms): the deferred kernel feeds each shadow tile to two A
-    // operands (its LDS is static: any k <= 64); the inline kernel splits its waves in two
-    // halves where the item's lists fit its LDS, else it runs 16-query items.
-    uint32_t screen_width(uint32_t k, uint32_t P) const {
-        if (!screen_ready || metric == 2 || vdbk::topk_regs(k) != 1) return 0;
-        if (tiered() && !screen_defer) return 0;    // (the tier's screen is the deferred one)
-        if (!screen_defer && screen_fmt_i8) return 0;  // (the inline kernel reads a bf16 shadow)
-        const uint32_t want = screen_group ? screen_group : (screen_defer && P >= 64 ? 32u : 16u);
-        if (want == 32 && vdbk::scan_screen_fits(k, dp, 32, screen_defer)) return 32;
-        return vdbk::scan_screen_fits(k, dp, 16, screen_defer) ? 16 : 0;
+    // ---- the scan's routing and sizing: scan_route.hpp decides, from these plain copies ----
+    static constexpr ScanConsts kScanConsts{(uint32_t)vdbk::kMergeFan, (uint32_t)vdbk::kPlanMaxPairs,
+                                            vdbk::kPersistentBlocks, VDB_SCAN_DIAG};
+    ScanKnobs knobs() const {
+        ScanKnobs kn;
+        kn.wide_scan = wide_scan;
+        kn.wide_group = wide_group;
+        kn.fused_scan = fused_scan;
+        kn.scan_mfma_min = scan_mfma_min;
+        kn.scan_blocks = scan_blocks;
+        kn.segs_item_opt = segs_item_opt;
+        kn.narrow_blocks = narrow_blocks;
+        kn.screen_group = screen_group;
+        kn.screen_defer = screen_defer;
+        kn.screen_i8 = screen_i8;
+        kn.screen_recheck2 = screen_recheck2;
+        kn.screen_thr_every = screen_thr_every;
+        kn.screen_cand_cap = screen_cand_cap;
+        kn.tier_cand_cap = tier_cand_cap;
+        return kn;
+    }
+    ScanFacts facts() const {
+        ScanFacts fa;
+        fa.metric = metric;
+        fa.seg_blocks = seg_blocks;
+        fa.screen_segs_auto = screen_segs_auto;
+        fa.screen_ready = screen_ready;
+        fa.screen_fmt_i8 = screen_fmt_i8;
+        fa.i8_vetoed = i8_vetoed;
+        fa.arena_dropped = arena_dropped;
+        fa.force_exact = force_exact;
+        fa.calibrating = calibrating;
+        fa.tiered = tiered();
+        fa.file_home = file_home();
+        return fa;
+    }
+    ScanFits fits(uint32_t k) const {
+        return {vdbk::topk_regs(k),
+                vdbk::scan_wide_fits(d4, k, 4),
+                vdbk::scan_wide_fits(d4, k, 8),
+                vdbk::scan_bounded_fits(d4, k),
+                vdbk::scan_screen_fits(k, dp, 16, screen_defer),
+                vdbk::scan_screen_fits(k, dp, 32, screen_defer)};
     }
     // The screen serves a search with this k and nprobe (the tier: the deferred scan with its
     // shadow resident; built lazily, so a stale screen is rebuilt first).
-    static constexpr uint32_t kCollectBlocks = 320;
     bool screen_serves(uint32_t k, uint32_t P) {
         last_P = P;
         if (screen_stale) screen_update();
-        return screen_width(k, P) != 0;
+        return vdbe::screen_width(knobs(), facts(), fits(k), P) != 0;
     }
-
-    // Queries per internal batch: the option `batch`, bounded so that batch x nprobe fits the
-    // plan kernel (8192 pairs) and so that one slot's per-segment partials (B x the segments
-    // of the P largest lists x k x 12 bytes) stay within kPartialBytes: the exact path at
-    // k = 1000 on the 10M x 768 index would otherwise hold 1.5 GB of partials per slot.
-    // Results never depend on batch boundaries.
-    static constexpr uint64_t kPartialBytes = 384ull << 20;
-    uint32_t batch_cap(uint32_t P, uint32_t k) const {
-        uint32_t b = std::max<uint32_t>(1, std::min<uint32_t>(batch, vdbk::kPlanMaxPairs / P));
-        const uint64_t per_query = (P < nseg_prefix.size() ? nseg_prefix[P] : 0) * (uint64_t)k * 12;
-        if (per_query) b = std::max<uint32_t>(1, (uint32_t)std::min<uint64_t>(b, kPartialBytes / per_query));
-        return b;
-    }
+    uint32_t batch_cap(uint32_t P, uint32_t k) const { return vdbe::batch_cap(kScanConsts, batch, nseg_prefix, P, k); }
 
     // Grow a slot-owned buffer; a buffer still read by the slot's previous call is
     // only freed once that call is done.
@@ -2605,19 +2535,30 @@ struct vdb_ivf {
             end_call(w, s);
             return;
         }
-        if (tiered() && lc.resident_lists() < storable_n && !screen_serves(k, P)) {  // (every stored list cached: the plain path)
+        if (through_tier(k, P))
             search_tiered(w, d_q, n, P, k, d_dist, d_ids, s, req_start);
-            end_call(w, s);
-            return;
-        }
+        else
+            plain_batches(w, d_q, n, P, k, d_dist, d_ids, s, req_start, xchg);
+        end_call(w, s);
+    }
+
+    // The tier serves a search through its list cache when some stored list is not cached
+    // (every one cached: the plain path) and the screen does not serve it.
+    bool through_tier(uint32_t k, uint32_t P) {
+        return tiered() && lc.resident_lists() < storable_n && !screen_serves(k, P);
+    }
+    // A call's queries in batches of at most batch_cap, results at od / oi ([n][k]);
+    // xchg_each: every batch goes through the slot's record and one exchange of its own.
+    void plain_batches(SearchSlot& w, const float* d_q, uint32_t n, uint32_t P, uint32_t k, float* od, uint64_t* oi,
+                       hipStream_t s, const uint32_t* req_start, bool xchg_each = false) {
         const uint32_t bmax = batch_cap(P, k);
         for (uint32_t b0 = 0, B = std::min(bmax, n); b0 < n; b0 += B, B = std::min(B, n - b0)) {
-            float* od = xchg ? rec_dist(w) : d_dist + (size_t)b0 * k;
-            uint64_t* oi = xchg ? rec_ids(w, B, k) : d_ids + (size_t)b0 * k;
-            run_batch(w, d_q + (size_t)b0 * dim, B, P, k, od, oi, s, req_start, b0);
-            if (xchg) exchange(w, B, k, d_dist + (size_t)b0 * k, d_ids + (size_t)b0 * k, s);
+            float* bd = od + (size_t)b0 * k;
+            uint64_t* bi = oi + (size_t)b0 * k;
+            run_batch(w, d_q + (size_t)b0 * dim, B, P, k, xchg_each ? rec_dist(w) : bd, xchg_each ? rec_ids(w, B, k) : bi, s,
+                      req_start, b0);
+            if (xchg_each) exchange(w, B, k, bd, bi, s);
         }
-        end_call(w, s);
     }
 
     // This shard's partial results of a whole call (n queries) into the slot's packed
@@ -2627,14 +2568,10 @@ struct vdb_ivf {
         slot_buf(w, w.xrec, vdb_rank_record_bytes(n, k));
         float* rd = rec_dist(w);
         uint64_t* ri = rec_ids(w, n, k);
-        if (tiered() && lc.resident_lists() < storable_n && !screen_serves(k, P)) {
+        if (through_tier(k, P))
             search_tiered(w, d_q, n, P, k, rd, ri, s, req_start);
-            return;
-        }
-        const uint32_t bmax = batch_cap(P, k);
-        for (uint32_t b0 = 0, B = std::min(bmax, n); b0 < n; b0 += B, B = std::min(B, n - b0))
-            run_batch(w, d_q + (size_t)b0 * dim, B, P, k, rd + (size_t)b0 * k, ri + (size_t)b0 * k, s, req_start,
-                      b0);
+        else
+            plain_batches(w, d_q, n, P, k, rd, ri, s, req_start);
     }
 
     // ONE all-gather of the slot's packed record (B queries) over the attached
