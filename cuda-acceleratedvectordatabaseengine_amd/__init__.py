@@ -30,10 +30,14 @@ _lib = None
 
 
 class Metric(enum.IntEnum):
-    """kernels::Metric (engine/kernels.cuh:24-28)."""
+    """kernels::Metric (engine/kernels.cuh:24-28), and this engine's own CosineDistance: true
+    cosine distance, an inner-product index over unit rows whose distances are reported as
+    1.0f + (-dot) (include/vdb_ivf.h, VDB_METRIC_COSINE_DISTANCE). Cosine (2) stays the
+    reference CPU path's 0.0f."""
     L2 = 0
     InnerProduct = 1
     Cosine = 2
+    CosineDistance = 3
 
 
 class VdbError(RuntimeError):
@@ -181,6 +185,7 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_stream": (vp, [vp]),
         "vdb_gen_normal_device": (ctypes.c_int, [vp, u64, u64, u64, vp]),
         "vdb_gen_mixture_device": (ctypes.c_int, [vp, u64, u32, vp, u32, ctypes.c_float, u64, u64, vp]),
+        "vdb_unit_rows_device": (ctypes.c_int, [vp, u64, u32, vp, vp]),
         "vdb_comm_unique_id": (ctypes.c_int, [vp]),
         "vdb_ivf_attach_comm": (ctypes.c_int, [vp, vp, u32, u32]),
         "vdb_ivf_detach_comm": (ctypes.c_int, [vp]),
@@ -237,6 +242,13 @@ def shard_plan_probe_weighted(list_sizes, probe_counts, n_sample: int, batch: in
 def gen_normal_device(ptr: int, n: int, seed: int, offset: int = 0, stream: int | None = None):
     """Fill n fp32 at device address ``ptr`` with deterministic N(0,1) draws."""
     _check(lib().vdb_gen_normal_device(ctypes.c_void_p(ptr), n, seed, offset, ctypes.c_void_p(stream or 0)))
+
+
+def unit_rows_device(in_ptr: int, n: int, dim: int, out_ptr: int, stream: int | None = None):
+    """unit(row) of Metric.CosineDistance for the n x dim fp32 rows at device address ``in_ptr``
+    into the n x dim rows at ``out_ptr`` (may not alias the input, which is only read)."""
+    _check(lib().vdb_unit_rows_device(ctypes.c_void_p(in_ptr), n, dim, ctypes.c_void_p(out_ptr),
+                                      ctypes.c_void_p(stream or 0)))
 
 
 def gen_mixture_device(ptr: int, rows: int, dim: int, centers_ptr: int, ncomp: int, sigma: float, seed: int,

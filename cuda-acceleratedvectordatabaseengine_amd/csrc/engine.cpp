@@ -34,6 +34,13 @@ inline void no_group(const vdb_ivf* h, const char* what) {
 // under the handle's lock, before they start: every prepared filter of the handle is stale from
 // then on, whether the call succeeds or not (filter_epoch.hpp; the list is in DESIGN 7f).
 inline void rows_may_move(const vdb_ivf* h) { filter_epochs().bump(h); }
+
+// Metric::CosineDistance is one-GPU in this version: a sharded rank hands out partials the
+// caller merges by (distance, id) (vdb_merge_ranks_*), and mapped distances would merge in
+// another order than one GPU gives. Refused before anything changes.
+inline void no_unit_rows(const vdb_ivf* h, const char* what) {
+    require(!h->unit_rows, std::string(what) + " is not available with VDB_METRIC_COSINE_DISTANCE", VDB_ERR_UNSUPPORTED);
+}
 }  // namespace vdbe
 
 extern "C" {
@@ -57,7 +64,7 @@ int vdb_ivf_create(const vdb_ivf_config* cfg, vdb_ivf** out) {
         require(cfg && out, "null argument");
         // ivf_flat_index.cpp:17-19
         require(cfg->dimension > 0 && cfg->nlist > 0, "Invalid configuration: dimension and nlist must be > 0");
-        require(cfg->metric >= 0 && cfg->metric <= 2, "unknown metric");
+        require(cfg->metric >= 0 && cfg->metric <= VDB_METRIC_COSINE_DISTANCE, "unknown metric");
         require(cfg->nlist < (1u << 19) - 1, "nlist above 524286 is not supported", VDB_ERR_UNSUPPORTED);
         auto* h = new vdb_ivf();
         try {
@@ -67,7 +74,9 @@ int vdb_ivf_create(const vdb_ivf_config* cfg, vdb_ivf** out) {
             // load is unconditional (the +0.0f pad terms leave every sum's bits unchanged)
             h->d4 = (cfg->dimension + 4 * vdbk::kTileAlign - 1) / (4 * vdbk::kTileAlign) * vdbk::kTileAlign;
             h->dp = h->d4 * 4;
-            h->metric = cfg->metric;
+            // CosineDistance: the inner-product machinery over unit rows (engine.hpp unit_rows)
+            h->unit_rows = cfg->metric == VDB_METRIC_COSINE_DISTANCE;
+            h->metric = h->unit_rows ? (int)VDB_METRIC_INNER_PRODUCT : cfg->metric;
             h->device = cfg->device;
             h->max_gpu_memory = cfg->max_gpu_memory == ~0ull ? 0 : cfg->max_gpu_memory;  // 0: no cap
             h->set_device();
@@ -270,6 +279,7 @@ int vdb_ivf_plan_shard(vdb_ivf* h, uint32_t rank, uint32_t world, const uint64_t
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         no_group(h, "plan_shard");
+        no_unit_rows(h, "plan_shard");
         rows_may_move(h);
         h->plan_shard(rank, world, final_sizes);
     });
@@ -308,11 +318,11 @@ int vdb_ivf_save(vdb_ivf* h, const char* path) {
         };
         try {
             if (shard_file) {
-                const uint32_t hdr[6] = {h->dim, h->nlist, (uint32_t)h->metric, h->rank, h->world, 0};
+                const uint32_t hdr[6] = {h->dim, h->nlist, (uint32_t)h->config_metric(), h->rank, h->world, 0};
                 put("VDBIVS01", 8);
                 put(hdr, sizeof(hdr));
             } else {
-                const uint32_t hdr[4] = {h->dim, h->nlist, (uint32_t)h->metric, 0};
+                const uint32_t hdr[4] = {h->dim, h->nlist, (uint32_t)h->config_metric(), 0};
                 put("VDBIVF01", 8);
                 put(hdr, sizeof(hdr));
             }
@@ -375,7 +385,7 @@ int vdb_ivf_load(vdb_ivf* h, const char* path) {
             throw VdbError(VDB_ERR_INVALID_ARGUMENT, "a shard file holds one rank's lists: serve it with open_lists");
         }
         if (std::memcmp(magic, "VDBIVF01", 8) != 0 || hdr[0] != h->dim || hdr[1] != h->nlist ||
-            (int)hdr[2] != h->metric) {
+            (int)hdr[2] != h->config_metric()) {
             std::fclose(f);
             throw VdbError(VDB_ERR_INVALID_ARGUMENT, "index file does not match this index's configuration");
         }
@@ -408,6 +418,16 @@ int vdb_ivf_load(vdb_ivf* h, const char* path) {
             else h->set_centroids_host(cc);
         };
         set_c(c.data());
+        // (CosineDistance: a file's rows are unit rows already and go in as stored)
+        struct Stored {
+            vdb_ivf* h;
+            void set(bool v) {
+                h->ingest_stored = v;
+                for (auto& mb : h->members) mb->ingest_stored = v;
+            }
+            explicit Stored(vdb_ivf* hh) : h(hh) { set(true); }
+            ~Stored() { set(false); }
+        } stored(h);
         try {
             if (h->is_group()) group::add_host(h, vs.data(), is.data(), ls.data(), is.size());
             else h->add_to_lists_host(vs.data(), is.data(), ls.data(), is.size());
@@ -578,6 +598,7 @@ int vdb_ivf_set_shard(vdb_ivf* h, uint32_t rank, uint32_t world) {
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         no_group(h, "set_shard");
+        no_unit_rows(h, "set_shard");
         rows_may_move(h);
         h->set_shard(rank, world);
     });
@@ -688,6 +709,7 @@ int vdb_ivf_set_shard_owners(vdb_ivf* h, uint32_t rank, uint32_t world, const ui
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         no_group(h, "set_shard");
+        no_unit_rows(h, "set_shard");
         rows_may_move(h);
         h->set_shard(rank, world, owner);
     });
@@ -700,6 +722,7 @@ int vdb_ivf_plan_shard_owners(vdb_ivf* h, uint32_t rank, uint32_t world, const u
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         no_group(h, "plan_shard");
+        no_unit_rows(h, "plan_shard");
         rows_may_move(h);
         h->plan_shard(rank, world, final_sizes, owner);
     });
@@ -1050,6 +1073,15 @@ int vdb_ivf_open_lists(vdb_ivf* h, const char* path) {
         require(h && path, "null argument");
         std::lock_guard<std::mutex> g(h->mu);
         no_group(h, "open_lists");
+        if (h->unit_rows) {  // (a shard file: refused before the handle's home changes)
+            char magic[8] = {};
+            if (FILE* f = std::fopen(path, "rb")) {
+                const size_t got = std::fread(magic, 1, 8, f);
+                std::fclose(f);
+                require(got != 8 || std::memcmp(magic, "VDBIVS01", 8) != 0,
+                        "opening a shard file is not available with VDB_METRIC_COSINE_DISTANCE", VDB_ERR_UNSUPPORTED);
+            }
+        }
         h->set_device();
         rows_may_move(h);
         h->open_lists(path);
@@ -1179,6 +1211,19 @@ int vdb_gen_mixture_device(float* d_out, uint64_t rows, uint32_t dim, const floa
     return guarded([&] {
         require((d_out && d_centers && ncomp > 0) || rows == 0, "invalid argument");
         vdbk::launch_gen_mixture(d_out, rows, dim, d_centers, ncomp, sigma, seed, row0, (hipStream_t)stream);
+        HIPCHECK(hipGetLastError());
+    });
+}
+
+int vdb_unit_rows_device(const float* d_in, uint64_t n, uint32_t dim, float* d_out, void* stream) {
+    return guarded([&] {
+        require((d_in && d_out) || n == 0, "null argument");
+        require(dim > 0 || n == 0, "dim must be > 0");
+        if (n == 0) return;
+        const uint64_t bytes = n * (uint64_t)dim * 4;
+        require((const char*)d_out + bytes <= (const char*)d_in || (const char*)d_in + bytes <= (const char*)d_out,
+                "d_out may not alias d_in");
+        vdbk::launch_unit_rows(d_in, n, dim, dim, d_out, (hipStream_t)stream);
         HIPCHECK(hipGetLastError());
     });
 }

@@ -44,6 +44,7 @@
 #include "list_cache.hpp"
 #include "row_reader.hpp"
 #include "scan_route.hpp"
+#include "unit_kernels.hpp"
 #include "uring.hpp"
 
 namespace vdbe {
@@ -258,6 +259,16 @@ using namespace vdbe;
 struct vdb_ivf {
     uint32_t dim = 0, nlist = 0, dp = 0, d4 = 0;
     int metric = 0;
+    // Metric::CosineDistance (3): an inner-product handle (metric = kIP: no kernel dispatch ever
+    // sees a 3) over unit rows. Every ingested row is normalised once in padded_rows, every
+    // batch's queries in stage_queries (launch_unit_rows), and a call's final distances are
+    // mapped by 1.0f + d (cos_finish). Lists, save files and the tier's homes hold unit rows.
+    bool unit_rows = false;
+    // Rows that are unit rows already (vdb_ivf_load feeds a file's stored rows back through
+    // add_to_lists_host): unit() is not idempotent bit for bit, so they are only padded.
+    bool ingest_stored = false;
+    // What the handle was configured with (save header, load / open_lists checks, attach_comm).
+    int config_metric() const { return unit_rows ? 3 : metric; }
     int device = 0;
     uint64_t max_gpu_memory = 0;
     hipStream_t stream = nullptr;
@@ -1550,7 +1561,7 @@ struct vdb_ivf {
             throw VdbError(VDB_ERR_INVALID_ARGUMENT, why);
         };
         if ((!shard_file && std::memcmp(magic, "VDBIVF01", 8) != 0) || hdr[0] != dim || hdr[1] != nlist ||
-            (int)hdr[2] != metric)
+            (int)hdr[2] != config_metric())
             refuse("index file does not match this index's configuration");
         if (shard_file && (hdr[4] == 0 || hdr[3] >= hdr[4])) refuse("shard file with an invalid (rank, world)");
         const uint64_t hdr_bytes = shard_file ? 32 : 24;
@@ -1643,8 +1654,14 @@ struct vdb_ivf {
         tier_by_cap = true;
     }
 
-    // Row-major [n][dim] device input -> zero-padded [n][dp] (or the input itself).
+    // Row-major [n][dim] device input -> zero-padded [n][dp] (or the input itself). With
+    // unit_rows: the unit rows, always in tmp (the caller's buffer is never written).
     const float* padded_rows(const float* d_v, uint64_t n, DevBuf<float>& tmp) {
+        if (unit_rows && !ingest_stored) {
+            vdbk::launch_unit_rows(d_v, n, dim, dp, tmp.ensure(n * dp), stream);
+            HIPCHECK(hipGetLastError());
+            return tmp.p;
+        }
         if (dp == dim) return d_v;
         vdbk::launch_pad_rows(d_v, n, dim, dp, tmp.ensure(n * dp), stream);
         HIPCHECK(hipGetLastError());
@@ -1819,6 +1836,16 @@ struct vdb_ivf {
             vdbk::launch_centroid_update(vpad, dp, order.p, offsets.p, counts.p, nlist, dim, cent_rm.p, stream);
             HIPCHECK(hipGetLastError());
             HIPCHECK(hipStreamSynchronize(stream));
+        }
+        if (unit_rows) {
+            // spherical k-means' last step: the final centroids to unit length, by the rows'
+            // kernel (the +0 pads add nothing to a sum: the bits are those of the dim-long row);
+            // a zero centroid stays zero
+            DevBuf<float> cu;
+            vdbk::launch_unit_rows(cent_rm.p, nlist, dp, dp, cu.ensure((size_t)nlist * dp), stream);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipMemcpyAsync(cent_rm.p, cu.p, (size_t)nlist * dp * 4, hipMemcpyDeviceToDevice, stream));
+            HIPCHECK(hipStreamSynchronize(stream));  // (cu goes on return)
         }
         refresh_centroid_layout();
         HIPCHECK(hipStreamSynchronize(stream));
@@ -2005,7 +2032,14 @@ struct vdb_ivf {
     // already a multiple of the padding (768) the caller's rows are used in place (they
     // stay valid until the stream passes the search, as for any asynchronous call), else
     // a padded copy in w.qpad.
+    // With unit_rows: the unit queries, always in w.qpad (ensure_workspace sizes it [B][dp]
+    // whatever dim is); the caller's rows are only read.
     void stage_queries(SearchSlot& w, const float* d_q, uint32_t B, hipStream_t s) {
+        if (unit_rows) {
+            vdbk::launch_unit_rows(d_q, B, dim, dp, w.qpad.p, s);
+            w.q = w.qpad.p;
+            return;
+        }
         if (dim == dp && ((uintptr_t)d_q & 15) == 0) {  // (rows are read as float4)
             w.q = d_q;
             return;
@@ -2514,7 +2548,10 @@ struct vdb_ivf {
         }
         require(P <= (uint32_t)vdbk::kMaxK, "nprobe above 1024 is not supported", VDB_ERR_UNSUPPORTED);
         if (is_group()) {
+            // (the members, reached through run_batch / call_to_record, hand out -dot partials;
+            // the mapping follows the group's merge)
             group_search_device(d_q, n, P, k, d_dist, d_ids, s, req_start);
+            cos_finish(d_dist, d_ids, (uint64_t)n * k, s);
             return;
         }
         const bool xchg = comm != nullptr;
@@ -2539,7 +2576,16 @@ struct vdb_ivf {
             search_tiered(w, d_q, n, P, k, d_dist, d_ids, s, req_start);
         else
             plain_batches(w, d_q, n, P, k, d_dist, d_ids, s, req_start, xchg);
+        cos_finish(d_dist, d_ids, (uint64_t)n * k, s);
         end_call(w, s);
+    }
+
+    // unit_rows: the call's final [n][k] distances, after the last merge (the batches' stale
+    // carries hold -dot and never read the output), mapped by 1.0f + d where an id is filled.
+    void cos_finish(float* d_dist, const uint64_t* d_ids, uint64_t nk, hipStream_t s) {
+        if (!unit_rows) return;
+        vdbk::launch_cos_finish(d_dist, d_ids, nk, s);
+        HIPCHECK(hipGetLastError());
     }
 
     // The tier serves a search through its list cache when some stored list is not cached

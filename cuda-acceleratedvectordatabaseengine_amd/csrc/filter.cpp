@@ -207,6 +207,7 @@ void search_masked(vdb_ivf& h, const float* queries, uint32_t n, uint32_t nprobe
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipEventRecord(ev[2], s));
     }
+    h.cos_finish(d_out_d.p, d_out_i.p, nk, s);  // (CosineDistance: after the last merge; the carry holds -dot)
     HIPCHECK(hipMemcpyAsync(distances, d_out_d.p, nk * 4, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipMemcpyAsync(ids, d_out_i.p, nk * 8, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipMemcpyAsync(&pairs, d_pairs.p, 8, hipMemcpyDeviceToHost, s));

@@ -503,6 +503,8 @@ int vdb_ivf_attach_comm(vdb_ivf* h, const void* id, uint32_t rank, uint32_t worl
     return guarded([&] {
         require(h && id && world > 0 && rank < world, "invalid argument");
         require(!h->is_group(), "a group handle owns its communicators", VDB_ERR_STATE);
+        // (a rank's partials merge by (distance, id): mapped distances would merge in another order)
+        require(!h->unit_rows, "attach_comm is not available with VDB_METRIC_COSINE_DISTANCE", VDB_ERR_UNSUPPORTED);
         std::lock_guard<std::mutex> g(h->mu);
         // (exchange_emulate_world: a shard's handle times its exchange on a communicator of
         // world 1, records of W ranks' size; diagnostics of one rank's timeline)
@@ -545,7 +547,7 @@ int vdb_ivf_attach_comm(vdb_ivf* h, const void* id, uint32_t rank, uint32_t worl
                 if (h->owned[l] && h->count[l]) mine[5 + l / 64] |= 1ull << (l % 64);
             }
             mine[0] = ((uint64_t)h->dim << 32) | h->nlist;
-            mine[1] = ((uint64_t)(uint32_t)h->metric << 32) | h->batch;
+            mine[1] = ((uint64_t)(uint32_t)h->config_metric() << 32) | h->batch;
             mine[2] = (uint64_t)h->stale;  // (the tier may differ between ranks: exchanges are per call)
             mine[3] = fnv;
             mine[4] = h->total;

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "cosine_map.hpp"
 #include "exact_call.hpp"
 #include "range_kernels.hpp"
 
@@ -97,6 +98,11 @@ std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries,
     if (P == 0 || h.arena_blocks == 0 || h.total == 0) return res;
     (void)resident_lists(h);  // (refused before any device work)
 
+    // CosineDistance: the radius is in mapped distances; the scan thresholds the handle's own
+    // -dot at the largest t with fl(1.0f + t) <= radius, and the hits are mapped on the way out
+    // (on the host: the same IEEE add as launch_cos_finish). The order stays (-dot, id).
+    const float scan_radius = h.unit_rows ? cos_threshold(radius) : radius;
+
     hipStream_t s = h.stream;
     DevBuf<uint32_t> d_start;
     ScanGroupBufs grp;
@@ -136,7 +142,7 @@ std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries,
             fill_scan_list_args(a, h, w, grp, B, P, segs);
             a.allow = d_allow;
             a.allowed = d_allowed;
-            a.radius = radius;
+            a.radius = scan_radius;
             a.cap = hit.cap;
             a.hit_key = hit.key_a;
             a.hit_id = hit.id_a;
@@ -192,6 +198,8 @@ std::unique_ptr<vdb_range_result> range_search(vdb_ivf& h, const float* queries,
                 HIPCHECK(hipMemcpyAsync(res->ids.data() + at, o.key_b, kept * 8, hipMemcpyDeviceToHost, s));
                 HIPCHECK(hipMemcpyAsync(res->distances.data() + at, o.perm_a, kept * 4, hipMemcpyDeviceToHost, s));
                 HIPCHECK(hipStreamSynchronize(s));
+                if (h.unit_rows)
+                    for (uint64_t i = at; i < at + kept; ++i) res->distances[i] = cos_map(res->distances[i]);
             }
         } else {
             std::fill(start.begin(), start.end(), 0u);

@@ -25,7 +25,8 @@
  * caller-owned and row-major (queries n x dim fp32; outputs n x k). Metric
  * ordinals follow kernels::Metric (engine/kernels.cuh:24-28): L2 = 0 (squared
  * L2), InnerProduct = 1 (negated dot), Cosine = 2 (the reference CPU path leaves
- * its distance at 0.0f, ivf_flat_index.cpp:351-362; mirrored exactly).
+ * its distance at 0.0f, ivf_flat_index.cpp:351-362; mirrored exactly);
+ * CosineDistance = 3 is this engine's own (true cosine distance, see below).
  * Unfilled result slots are (FLT_MAX, UINT64_MAX) as in ivf_flat_index.cpp:513-517.
  * Results are bit-identical to the reference CPU path (ids and distance bits).
  * No torch or HIP types appear in these signatures; streams are passed as void*.
@@ -49,7 +50,52 @@ enum {
     VDB_ERR_STATE = -5
 };
 
-enum { VDB_METRIC_L2 = 0, VDB_METRIC_INNER_PRODUCT = 1, VDB_METRIC_COSINE = 2 };
+enum { VDB_METRIC_L2 = 0, VDB_METRIC_INNER_PRODUCT = 1, VDB_METRIC_COSINE = 2, VDB_METRIC_COSINE_DISTANCE = 3 };
+
+/*
+ * VDB_METRIC_COSINE_DISTANCE (3): true cosine distance, 1 - cos(query, row). Ordinal 2 keeps the
+ * reference CPU path's behaviour (0.0f everywhere), bit for bit.
+ *
+ * Definition. A handle created with metric 3 is an inner-product handle over UNIT ROWS: every
+ * row is normalised once when it enters the index (train, add, add_device, add_to_lists,
+ * add_to_lists_device, assign_device, a group's add), every query when it enters a batch, and
+ * every filled result distance d (the inner-product handle's -dot) is reported as 1.0f + d, one
+ * fp32 add. Every call's result is exactly the result of the same call on an InnerProduct handle
+ * with the same centroids that stores unit(row) for each row and is asked unit(query), each
+ * distance whose id is not UINT64_MAX then replaced by 1.0f + d; unfilled slots stay
+ * (FLT_MAX, UINT64_MAX). Order, the unique-id merge, stale_slots, nprobe clamping, k limits and
+ * the refusals are the InnerProduct handle's, unchanged. The screened scan, the list-cache tier
+ * (host home, or vdb_ivf_open_lists of a plain metric-3 file), groups, remove_ids, filters and
+ * prepared filters serve it as they serve inner product.
+ *
+ * Order. Entries stay ordered by (-dot, id); they are NOT re-sorted by the mapped value.
+ * fl(1 + d) is monotone but collapses neighbours: two entries with distinct -dot may report
+ * equal distances, and then stand in -dot order, not id order.
+ *
+ * unit(x), fixed so that a host restatement gives the same bits (tests/cosine_ref.py): with
+ * j = i / 4, element i belongs to lane j % 64; a lane adds the squares of its elements in
+ * ascending i (fp32, product rounded, then sum rounded, no fused multiply-add); the 64 partials
+ * combine by p[l] += p[l + s] for s = 32, 16, 8, 4, 2, 1; norm = sqrt of that sum, correctly
+ * rounded; if norm is finite and > 0 every element becomes x[i] / norm (a correctly rounded
+ * division), otherwise (a zero row, an overflowing sum, a NaN) the row is kept as it is.
+ * Denormal intermediates are unspecified. This deliberately differs from the reference's
+ * unported GPU functor (kernels.cuh:63-80), which adds 1e-8 to a per-pair product of norms.
+ *
+ * Stored rows. vdb_ivf_get_list, save files and the tier's homes hold unit rows. unit() is not
+ * idempotent bit for bit, so rows are normalised exactly once: vdb_ivf_load stores a file's rows
+ * as they are. vdb_ivf_train runs the reference algorithm on the unit rows and then normalises
+ * the final centroids (spherical k-means' last step; a zero centroid stays zero);
+ * vdb_ivf_set_centroids stores what it is given. A save file records metric 3: it loads only
+ * into a metric-3 handle, and no L2 / InnerProduct / Cosine file loads into one.
+ *
+ * Range search. The radius is in reported distances: the scan thresholds -dot at the largest
+ * fp32 t with fl(1.0f + t) <= radius, and returned distances are 1.0f + d.
+ *
+ * Refused in this version with VDB_ERR_UNSUPPORTED, the handle untouched: vdb_ivf_set_shard*,
+ * vdb_ivf_plan_shard*, vdb_ivf_attach_comm and opening a shard file. A sharded rank hands out
+ * partials the caller merges by (distance, id) with vdb_merge_ranks_*; mapped distances would
+ * merge in another order than one GPU gives.
+ */
 
 typedef struct vdb_ivf vdb_ivf;
 
@@ -542,6 +588,12 @@ int vdb_gen_normal_device(float* d_out, uint64_t n, uint64_t seed, uint64_t offs
  * device) + sigma * N(0,1). Independent of how the rows are split into calls. */
 int vdb_gen_mixture_device(float* d_out, uint64_t rows, uint32_t dim, const float* d_centers, uint32_t ncomp,
                            float sigma, uint64_t seed, uint64_t row0, void* stream);
+
+/* unit(row) of VDB_METRIC_COSINE_DISTANCE for n device rows (d_in, n x dim) into d_out (n x dim,
+ * device; may not alias d_in, which is only read): the kernel a metric-3 handle applies to every
+ * ingested row and every query, for callers who normalise themselves (an InnerProduct handle
+ * fed these rows and queries gives the metric-3 handle's results before the 1.0f + d map). */
+int vdb_unit_rows_device(const float* d_in, uint64_t n, uint32_t dim, float* d_out, void* stream);
 
 #ifdef __cplusplus
 }
