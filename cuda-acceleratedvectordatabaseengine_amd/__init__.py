@@ -177,6 +177,8 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_survivor_histogram": (ctypes.c_int, [vp, vp]),
         "vdb_ivf_collect_stamps": (ctypes.c_int, [vp, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                                   ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_screen_snapshot": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64,
+                                                   ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_ivf_open_lists": (ctypes.c_int, [vp, ctypes.c_char_p]),
         "vdb_ivf_profile_enable": (ctypes.c_int, [vp, i32]),
         "vdb_ivf_profile_reset": (ctypes.c_int, [vp]),
@@ -744,6 +746,38 @@ class IVFFlatIndex:
         if n.value:
             _check(lib().vdb_ivf_collect_stamps(self._h, out.ctypes.data, n.value, ctypes.byref(n), ctypes.byref(hz)))
         return out, hz.value
+
+    _SNAPSHOT = {"probes": (np.uint32, ()), "sorted_pair": (np.uint32, ()), "counters": (np.uint32, ()),
+                 "cand": (np.uint32, (4,)), "ovf": (np.uint32, ()), "thr": (np.uint32, ()), "thr4": (np.uint32, (4,)),
+                 "ublist": (np.float32, ()), "ubcnt": (np.uint32, ()), "scnt": (np.uint32, ()),
+                 "soff": (np.uint32, ()), "surv": (np.uint32, (2,)), "pst": (np.float32, (4,)),
+                 "qscale": (np.float32, ()), "qres": (np.uint8, ()), "block_off": (np.uint64, ()),
+                 "count": (np.uint32, ()), "meta": (np.float32, (4,)), "sscale": (np.float32, ()),
+                 "shadow": (np.uint8, ())}
+    _SNAPSHOT_SCALARS = ("B", "P", "k", "dp", "seg_blocks", "segs_item", "wide_q", "cand_cap", "i8", "metric",
+                         "grid", "nlist", "blocks", "ub_lists", "cand_chunk", "dim", "slot", "cand_alloc")
+
+    def screen_snapshot_raw(self, name: str, dtype) -> np.ndarray:
+        """One named buffer of vdb_ivf_screen_snapshot as a flat array of dtype ("cand_alloc": the
+        slot's whole candidate allocation, not part of screen_snapshot())."""
+        n = ctypes.c_uint64(0)
+        _check(lib().vdb_ivf_screen_snapshot(self._h, name.encode(), None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value // np.dtype(dtype).itemsize, dtype=dtype)
+        if n.value:
+            _check(lib().vdb_ivf_screen_snapshot(self._h, name.encode(), out.ctypes.data, n.value, ctypes.byref(n)))
+        return out
+
+    def screen_snapshot(self) -> dict:
+        """(diagnostics) every buffer of the most recently issued deferred screened batch (rows in
+        HBM) and the handle's screen data, as numpy arrays, plus the batch's scalars as ints
+        (vdb_ivf_screen_snapshot; include/vdb_ivf.h has the layouts). thr / thr4 keep their
+        order-preserving encoding; qres and shadow are raw bytes. Changes nothing."""
+        fetch = self.screen_snapshot_raw
+        snap = {k: int(v) for k, v in zip(self._SNAPSHOT_SCALARS, fetch("scalars", np.uint64))}
+        for name, (dtype, tail) in self._SNAPSHOT.items():
+            snap[name] = fetch(name, dtype).reshape((-1,) + tail)
+        snap["ublist"] = snap["ublist"].reshape(snap["B"] * snap["P"], snap["ub_lists"], snap["k"])
+        return snap
 
     def profile_enable(self, on: bool = True):
         _check(lib().vdb_ivf_profile_enable(self._h, int(on)))

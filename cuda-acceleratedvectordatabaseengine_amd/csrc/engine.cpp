@@ -1041,6 +1041,70 @@ int vdb_ivf_collect_stamps(vdb_ivf* h, uint64_t* out, uint64_t cap, uint64_t* n,
     });
 }
 
+int vdb_ivf_screen_snapshot(vdb_ivf* h, const char* name, void* out, uint64_t cap_bytes, uint64_t* bytes) {
+    return guarded([&] {
+        require(name && bytes, "null argument");
+        static const char* const kNames[] = {"scalars", "probes", "sorted_pair", "counters", "cand", "ovf", "thr",
+                                             "thr4", "ublist", "ubcnt", "scnt", "soff", "surv", "pst", "qscale",
+                                             "qres", "block_off", "count", "meta", "sscale", "shadow", "cand_alloc"};
+        const std::string n = name;
+        bool known = false;
+        for (const char* kn : kNames) known |= n == kn;
+        if (!known) throw VdbError(VDB_ERR_INVALID_ARGUMENT, "unknown snapshot buffer " + n);
+        require(h, "null handle");
+        std::lock_guard<std::mutex> g(h->mu);
+        no_group(h, "screen_snapshot");
+        h->set_device();
+        h->quiesce();
+        HIPCHECK(hipStreamSynchronize(h->stream));
+        const auto& sn = h->snap;
+        // (a directory or list change since the batch marks the screen stale: its data is then not the batch's)
+        require(sn.ok && h->screen_ready && !h->screen_stale, "the last batch did not take the deferred screened route with rows in HBM");
+        const vdb_ivf::SearchSlot& w = h->slots[sn.slot];
+        const uint64_t BP = (uint64_t)sn.B * sn.P, blocks = h->arena_blocks;
+        const bool i8 = sn.i8 != 0;
+        uint32_t hc[vdbk::kCounters];
+        HIPCHECK(hipMemcpy(hc, w.counters.p, sizeof(hc), hipMemcpyDeviceToHost));
+        const uint64_t ncand = std::min<uint64_t>(hc[vdbk::kCtrCand], sn.cand_cap);
+        const uint64_t nsurv = std::min<uint64_t>(hc[vdbk::kCtrSurv], sn.cand_cap);
+        const uint64_t scalars[18] = {sn.B, sn.P, sn.k, h->dp, h->seg_blocks, sn.segs_item, sn.wide_q, sn.cand_cap,
+                                      sn.i8, (uint64_t)h->metric, sn.grid, h->nlist, blocks, (uint64_t)vdbk::kUbLists,
+                                      vdbk::kCandChunk, h->dim, (uint64_t)sn.slot, w.scand.cap};
+        const void* src = nullptr;
+        uint64_t sz = 0;
+        bool host = false;
+        auto dev = [&](const void* p, uint64_t b) { src = p, sz = b; };
+        if (n == "scalars") src = scalars, sz = sizeof(scalars), host = true;
+        else if (n == "counters") src = hc, sz = sizeof(hc), host = true;
+        else if (n == "probes") dev(w.probes.p, BP * 4);
+        else if (n == "sorted_pair") dev(w.sorted_pair.p, BP * 4);
+        else if (n == "cand") dev(w.scand.p, ncand * 16);
+        else if (n == "cand_alloc") dev(w.scand.p, (uint64_t)w.scand.cap * 16);  // (the slot's whole allocation)
+        else if (n == "ovf") dev(w.ovf.p, BP * 4);
+        else if (n == "thr") dev(w.thr.p, BP * 4);
+        else if (n == "thr4") dev(w.thr4.p, BP * 16);
+        else if (n == "ublist") dev(w.ublist.p, BP * vdbk::kUbLists * sn.k * 4);
+        else if (n == "ubcnt") dev(w.ubcnt.p, BP * 4);
+        else if (n == "scnt") dev(w.scnt.p, BP * 4);
+        else if (n == "soff") dev(w.soff.p, (BP + 1) * 4);
+        else if (n == "surv") dev(w.surv.p, nsurv * 8);
+        else if (n == "pst") dev(w.pst.p, BP * 16);
+        else if (n == "qscale") dev(w.qscale.p, i8 ? BP * 4 : 0);
+        else if (n == "qres") dev(w.qres.p, BP * h->dp * (i8 ? 1 : 2));
+        else if (n == "block_off") dev(h->d_block_off.p, (uint64_t)h->nlist * 8);
+        else if (n == "count") dev(h->d_count_local.p, (uint64_t)h->nlist * 4);
+        else if (n == "meta") dev(h->screen_meta.p, blocks * 64 * 16);
+        else if (n == "sscale") dev(h->screen_scale.p, i8 ? blocks * 64 * 4 : 0);
+        else dev(h->screen_sh.p, blocks * h->dp * 64 * (i8 ? 1 : 2));
+        *bytes = sz;
+        if (!out) return;  // (the size only)
+        require(cap_bytes >= sz, "snapshot buffer too small");
+        if (!sz) return;
+        if (host) std::memcpy(out, src, sz);
+        else HIPCHECK(hipMemcpy(out, src, sz, hipMemcpyDeviceToHost));
+    });
+}
+
 int vdb_ivf_survivor_histogram(vdb_ivf* h, uint64_t* out) {
     return guarded([&] {
         require(h && out, "null argument");

@@ -396,6 +396,14 @@ struct vdb_ivf {
     // (option collect_stamps, diagnostics) timeline records of the collect kernel's items
     DevBuf<unsigned long long> stamps_buf;
     uint32_t stamps_cap = 0, stamp_batch = 0;
+    // (vdb_ivf_screen_snapshot, diagnostics) the most recently issued batch: the slot that
+    // holds its buffers and the scalars its collect ran with; ok only for the deferred
+    // screened route with rows in HBM
+    struct ScreenSnap {
+        bool ok = false;
+        int slot = -1;
+        uint32_t B = 0, P = 0, k = 0, segs_item = 0, wide_q = 0, cand_cap = 0, i8 = 0, grid = 0;
+    } snap;
     uint64_t screen_tier_fallbacks = 0;
     bool force_exact = false;          // (that path's batches: never screened)
     // Run-time floor under the screen (lists in HBM; floor.hpp): every deferred batch reports
@@ -2077,6 +2085,7 @@ struct vdb_ivf {
         // (tier: lists and directory entries another stream loaded must have landed)
         if (tiered() && tier_ev_used) HIPCHECK(hipStreamWaitEvent(s, tier_ev, 0));
         last_P = P;
+        snap.ok = false;  // (set below by the deferred screened route with rows in HBM)
         if (screen_stale) screen_update();
         // The route (scan_route.hpp): screened (default, L2 / IP, k <= 64) in items of swq
         // queries unless the run-time floor (lists in HBM only) sends the batch to the exact
@@ -2224,6 +2233,11 @@ struct vdb_ivf {
                     ++screen_reruns;
                 }
                 if (tiered()) ++screen_tier_batches;
+                if (!tiered() && sa.rows && in_ring) {  // (what vdb_ivf_screen_snapshot reads)
+                    const uint32_t gmax = r.swq > 16 ? vdbk::kPersistentBlocks / 2 : vdbk::kPersistentBlocks;
+                    snap = ScreenSnap{true, (int)(&w - slots), B, P, k, r.segs(), r.swq, ccap, i8s ? 1u : 0u,
+                                      std::min<uint32_t>(r.grid_collect, gmax)};
+                }
                 if (tier2) {  // pass A's exact distances and pass B's marks; its rows; the pairs' top-k
                     vdbk::launch_tier_recheck(1, metric, sa, BP, w.nseg_qp.p, w.soff.p, w.scnt.p, w.surv.p, w.slb.p,
                                               w.smark.p, w.rowmap.p, w.srows.p, w.sdist.p, s);

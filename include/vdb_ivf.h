@@ -484,6 +484,23 @@ int vdb_ivf_survivor_histogram(vdb_ivf* index, uint64_t* out);
  * list << 32}; copies min(cap, *n) records, *clock_hz = the wall clock's rate, and resets the
  * buffer. Synchronises the handle. */
 int vdb_ivf_collect_stamps(vdb_ivf* index, uint64_t* out, uint64_t cap, uint64_t* n, uint64_t* clock_hz);
+/* Diagnostics: one named buffer of the most recently issued batch of the deferred screened
+ * scan (rows in HBM), read-only: synchronises the handle, copies the buffer to `out` (cap_bytes
+ * at least its size) and sets *bytes; out null: the size only. Nothing is changed. Per batch:
+ * "probes" u32[B P], "sorted_pair" u32[B P] (query << 16 | probe), "counters" u32 (the whole
+ * array), "cand" u32[n][4] {sorted pair, slot, lower bound bits, rank or ~0} for n = min(reserved,
+ * capacity), "ovf", "ubcnt", "scnt" u32[B P], "thr" u32[B P] and "thr4" u32[B P][4] (order-
+ * preserving float encoding), "ublist" f32[B P][lists][k], "soff" u32[B P + 1], "surv"
+ * u32[survivors][2] {slot, sorted pair}, "pst" f32[B P][4], "qscale" f32[B P] (int8 shadow; else
+ * empty), "qres" (int8 or bf16 [B P][dp]); per handle: "block_off" u64[nlist], "count"
+ * u32[nlist], "meta" f32[slots][4], "sscale" f32[slots] (int8), "shadow" (bytes); and "scalars"
+ * u64[18] {B, P, k, dp, seg_blocks, segs_item, wide_q, cand_cap, int8 shadow, metric, collect
+ * workgroups, nlist, blocks, upper-bound lists per pair, candidate chunk, dim, workspace slot,
+ * entries allocated for candidates}; "cand_alloc": the slot's whole candidate allocation (what
+ * lies past the capacity must never change).
+ * VDB_ERR_INVALID_ARGUMENT: a null or unknown name, a group handle, or a last batch that took
+ * another route (the inline screen, the exact scan, the tier). */
+int vdb_ivf_screen_snapshot(vdb_ivf* index, const char* name, void* out, uint64_t cap_bytes, uint64_t* bytes);
 /* The tier's home on disk (ListPrefetcher::register_list_file / prefetch_lists,
  * engine/prefetcher.h:139-183; list files of format/storage.h): serve this handle's lists
  * from an index file written by vdb_ivf_save, without reading them into memory.
