@@ -285,11 +285,7 @@ int vdb_ivf_plan_shard(vdb_ivf* h, uint32_t rank, uint32_t world, const uint64_t
     });
 }
 
-// Index file: "VDBIVF01", u32 dim, u32 nlist, i32 metric, u32 reserved, centroids
-// f32[nlist][dim], then per list: u64 count, u64 ids[count], f32 vectors[count][dim].
-// Shard file: "VDBIVS01", u32 dim, u32 nlist, i32 metric, u32 rank, u32 world, u32 reserved,
-// centroids, then per list: u64 count (global), u64 stored (count if the rank owns the
-// list, else 0), u64 ids[stored], f32 vectors[stored][dim].
+// The file's layout (an index file, or a shard file from a sharded handle): index_file.hpp.
 int vdb_ivf_save(vdb_ivf* h, const char* path) {
     return guarded([&] {
         require(h && path, "null argument");
@@ -317,19 +313,17 @@ int vdb_ivf_save(vdb_ivf* h, const char* path) {
             if (b && std::fwrite(p, 1, b, f) != b) throw VdbError(VDB_ERR_STATE, "short write");
         };
         try {
-            if (shard_file) {
-                const uint32_t hdr[6] = {h->dim, h->nlist, (uint32_t)h->config_metric(), h->rank, h->world, 0};
-                put("VDBIVS01", 8);
-                put(hdr, sizeof(hdr));
-            } else {
-                const uint32_t hdr[4] = {h->dim, h->nlist, (uint32_t)h->config_metric(), 0};
-                put("VDBIVF01", 8);
-                put(hdr, sizeof(hdr));
-            }
+            IndexFileHeader hd;
+            hd.shard = shard_file;
+            hd.dim = h->dim;
+            hd.nlist = h->nlist;
+            hd.metric = h->config_metric();
+            hd.rank = h->rank;
+            hd.world = h->world;
             std::vector<float> c((size_t)h->nlist * h->dim);
             h->head()->set_device();
             h->head()->export_centroids(c.data());
-            put(c.data(), c.size() * 4);
+            write_index_file_head(hd, c.data(), put);
             std::vector<float> v;
             std::vector<uint64_t> ids;
             for (uint32_t l = 0; l < h->nlist; ++l) {
@@ -340,10 +334,7 @@ int vdb_ivf_save(vdb_ivf* h, const char* path) {
                 vdb_ivf* st = h->store_of(l);  // (a group: the member storing the list)
                 st->set_device();
                 if (stored) st->export_list(l, v.data(), ids.data());
-                put(&cnt, 8);
-                if (shard_file) put(&stored, 8);
-                put(ids.data(), stored * 8);
-                put(v.data(), v.size() * 4);
+                write_index_file_list(hd, cnt, stored, ids.data(), v.data(), put);
             }
         } catch (...) {
             std::fclose(f);
@@ -368,43 +359,29 @@ int vdb_ivf_load(vdb_ivf* h, const char* path) {
             std::lock_guard<std::mutex> g(h->mu);
             require(h->total == 0, "load() needs an empty index (this one holds vectors)", VDB_ERR_STATE);
         }
-        FILE* f = std::fopen(path, "rb");
-        require(f != nullptr, std::string("cannot open ") + path, VDB_ERR_STATE);
-        auto get = [&](void* p, size_t b) {
-            if (b && std::fread(p, 1, b, f) != b) {
-                std::fclose(f);
-                throw VdbError(VDB_ERR_STATE, "truncated index file");
-            }
-        };
-        char magic[8];
-        uint32_t hdr[4];
-        get(magic, 8);
-        get(hdr, sizeof(hdr));
-        if (std::memcmp(magic, "VDBIVS01", 8) == 0) {
-            std::fclose(f);
-            throw VdbError(VDB_ERR_INVALID_ARGUMENT, "a shard file holds one rank's lists: serve it with open_lists");
-        }
-        if (std::memcmp(magic, "VDBIVF01", 8) != 0 || hdr[0] != h->dim || hdr[1] != h->nlist ||
-            (int)hdr[2] != h->config_metric()) {
-            std::fclose(f);
-            throw VdbError(VDB_ERR_INVALID_ARGUMENT, "index file does not match this index's configuration");
-        }
+        IndexFileFd f(path);
+        require(f.fd >= 0, std::string("cannot open ") + path, VDB_ERR_STATE);
+        // The directory first: every count below is bounded by the file's size.
+        IndexFileDirectory d;
+        index_file_checked([&] {
+            const IndexFileHeader hd = read_index_file_header(f, f.size);
+            require(!hd.shard, "a shard file holds one rank's lists: serve it with open_lists");
+            hd.require_config(h->dim, h->nlist, h->config_metric());
+            d = read_index_file_lists(hd, f, f.size);
+        });
         std::vector<float> c((size_t)h->nlist * h->dim);
-        get(c.data(), c.size() * 4);
-        std::vector<float> vs;
-        std::vector<uint64_t> is;
+        f(d.centroids_off, c.data(), d.centroid_bytes());
         std::vector<uint32_t> ls;
+        for (uint32_t l = 0; l < h->nlist; ++l) ls.insert(ls.end(), d.lists[l].count, l);
+        std::vector<float> vs(ls.size() * h->dim);
+        std::vector<uint64_t> is(ls.size());
+        uint64_t o = 0;
         for (uint32_t l = 0; l < h->nlist; ++l) {
-            uint64_t cnt = 0;
-            get(&cnt, 8);
-            const size_t o = is.size();
-            is.resize(o + cnt);
-            vs.resize((o + cnt) * h->dim);
-            get(is.data() + o, cnt * 8);
-            get(vs.data() + o * h->dim, cnt * h->dim * 4);
-            ls.insert(ls.end(), cnt, l);
+            const uint64_t cnt = d.lists[l].count;
+            f(d.ids_offset(l, 0), is.data() + o, cnt * sizeof(uint64_t));
+            f(d.row_offset(l, 0), vs.data() + o * h->dim, cnt * d.header.row_bytes());
+            o += cnt;
         }
-        std::fclose(f);
         std::lock_guard<std::mutex> g(h->mu);
         h->set_device();
         require(h->total == 0, "load() needs an empty index (this one holds vectors)", VDB_ERR_STATE);
@@ -1137,15 +1114,6 @@ int vdb_ivf_open_lists(vdb_ivf* h, const char* path) {
         require(h && path, "null argument");
         std::lock_guard<std::mutex> g(h->mu);
         no_group(h, "open_lists");
-        if (h->unit_rows) {  // (a shard file: refused before the handle's home changes)
-            char magic[8] = {};
-            if (FILE* f = std::fopen(path, "rb")) {
-                const size_t got = std::fread(magic, 1, 8, f);
-                std::fclose(f);
-                require(got != 8 || std::memcmp(magic, "VDBIVS01", 8) != 0,
-                        "opening a shard file is not available with VDB_METRIC_COSINE_DISTANCE", VDB_ERR_UNSUPPORTED);
-            }
-        }
         h->set_device();
         rows_may_move(h);
         h->open_lists(path);

@@ -41,6 +41,7 @@
 #include "../../include/vdb_ivf.h"
 #include "kernels.hpp"
 #include "floor.hpp"
+#include "index_file.hpp"
 #include "list_cache.hpp"
 #include "row_reader.hpp"
 #include "scan_route.hpp"
@@ -88,6 +89,51 @@ int guarded(F&& f) {
     } catch (const std::exception& e) {
         g_last_error = e.what();
         return VDB_ERR_DEVICE;
+    }
+}
+
+// `bytes` bytes of an index file at `off`, or a state error.
+inline void pread_exact(int fd, void* dst, size_t bytes, uint64_t off) {
+    char* p = (char*)dst;
+    while (bytes) {
+        const ssize_t r = ::pread(fd, p, bytes, (off_t)off);
+        require(r > 0, "short read from the list file", VDB_ERR_STATE);
+        p += r;
+        bytes -= (size_t)r;
+        off += (uint64_t)r;
+    }
+}
+
+// An open index file for index_file.hpp's reader: closed again unless its user takes fd.
+// A regular file is assumed: size is fstat's st_size, so anything that reports none there (a
+// block device, a failed fstat) has size 0 and is refused as truncated. bytes_read is what
+// open_lists adds to the handle's file_bytes_read.
+struct IndexFileFd {
+    int fd;
+    uint64_t size = 0, bytes_read = 0;
+    explicit IndexFileFd(const char* path, int flags = 0) : fd(::open(path, O_RDONLY | O_CLOEXEC | flags)) {
+        struct stat sb;
+        if (fd >= 0 && ::fstat(fd, &sb) == 0) size = (uint64_t)sb.st_size;
+    }
+    IndexFileFd(const IndexFileFd&) = delete;
+    ~IndexFileFd() {
+        if (fd >= 0) ::close(fd);
+    }
+    void operator()(uint64_t off, void* dst, size_t n) {
+        pread_exact(fd, dst, n, off);
+        bytes_read += n;
+    }
+};
+
+// Run f with index_file.hpp's refusals turned into the C ABI's errors.
+template <class F>
+void index_file_checked(F&& f) {
+    try {
+        f();
+    } catch (const IndexFileTruncated& e) {
+        throw VdbError(VDB_ERR_STATE, e.what());
+    } catch (const IndexFileRefused& e) {
+        throw VdbError(VDB_ERR_INVALID_ARGUMENT, e.what());
     }
 }
 
@@ -457,7 +503,7 @@ struct vdb_ivf {
     // most (a 3,072-B survivor row then reads 3,072 or 3,584 B), else 4096 (4 KiB-aligned
     // supersets, 1.5-2 pages per row)
     uint32_t dio_align = 4096;
-    std::vector<uint64_t> file_off;  // per list: file offset of its ids (vectors follow)
+    IndexFileDirectory home;         // where the file keeps each list (index_file.hpp)
     struct Stage {                   // one page-locked staging buffer of the read ring
         DevBuf<char> buf;
         hipEvent_t copied = nullptr;  // its H2D copies are done: the buffer may be refilled
@@ -1201,7 +1247,7 @@ struct vdb_ivf {
                 continue;
             }
             const uint32_t l = sblist_host[file[t].first >> 6];
-            reqs.push_back({file_off[l] + count[l] * 8 + (file[t].first - sblock_off[l] * 64) * row_bytes, file[t].second});
+            reqs.push_back({home.row_offset(l, file[t].first - sblock_off[l] * 64), file[t].second});
         }
         fetch_stage.host = true;
         float* st = fetch_stage.ensure((size_t)std::max<uint32_t>(nrows, 1) * dim);
@@ -1409,15 +1455,8 @@ struct vdb_ivf {
     bool file_home() const { return home_fd >= 0; }
 
     void pread_all(void* dst, size_t bytes, uint64_t off) {
-        char* p = (char*)dst;
-        while (bytes) {
-            const ssize_t r = ::pread(home_fd, p, bytes, (off_t)off);
-            require(r > 0, "short read from the list file", VDB_ERR_STATE);
-            p += r;
-            bytes -= (size_t)r;
-            off += (uint64_t)r;
-            file_bytes_read += (uint64_t)r;
-        }
+        pread_exact(home_fd, dst, bytes, off);
+        file_bytes_read += bytes;
     }
 
     // Copy planned lists into their cache blocks, ordered on stream s. Host-memory home:
@@ -1470,7 +1509,8 @@ struct vdb_ivf {
                 uring->read(home_fd, dst, (uint32_t)len, off, tag);
                 return 0;
             }
-            const uint64_t a0 = off & ~4095ull, a1 = (off + len + 4095) & ~4095ull;
+            uint64_t a0, a1;
+            aligned_superset(off, len, 4096, a0, a1);
             uring->read(home_fd_direct, dst, (uint32_t)(a1 - a0), a0, tag);
             return (size_t)(off - a0);
         };
@@ -1488,11 +1528,10 @@ struct vdb_ivf {
                         st.copying = false;
                     }
                     const Chunk& c = chunks[next++];
-                    const uint64_t base = file_off[c.l];
                     st.m = c.m;
                     st.dst_block = c.dst_block;
-                    st.ids_delta = read_into(si, st.buf.p, base + c.r0 * 8, c.m * 8, 0);
-                    st.vec_delta = read_into(si, st.buf.p + ids_cap, base + count[c.l] * 8 + c.r0 * dim * 4, c.m * dim * 4, 1);
+                    st.ids_delta = read_into(si, st.buf.p, home.ids_offset(c.l, c.r0), c.m * 8, 0);
+                    st.vec_delta = read_into(si, st.buf.p + ids_cap, home.row_offset(c.l, c.r0), c.m * dim * 4, 1);
                     st.reads = 2;
                     ++reading;
                     file_bytes_read += c.m * 8 + c.m * dim * 4;
@@ -1541,63 +1580,46 @@ struct vdb_ivf {
     void open_lists(const char* path) {
         require(tiered(), "open_lists needs the list-cache tier (set list_cache_bytes first)", VDB_ERR_STATE);
         quiesce();
-        const int fd = ::open(path, O_RDONLY | O_CLOEXEC);
-        require(fd >= 0, std::string("cannot open ") + path, VDB_ERR_STATE);
-        if (home_fd >= 0) ::close(home_fd);
-        if (home_fd_direct >= 0) ::close(home_fd_direct);
-        home_fd = fd;
+        // All or nothing: the file is opened, read and judged through locals, so a refusal or
+        // a read error closes them and leaves the handle serving what it served before.
+        IndexFileFd f(path);
+        require(f.fd >= 0, std::string("cannot open ") + path, VDB_ERR_STATE);
         // lists are read with O_DIRECT where the file system allows it (no page-cache copy)
-        home_fd_direct = ::open(path, O_RDONLY | O_CLOEXEC | O_DIRECT);
-        dio_align = 4096;
-        if (home_fd_direct >= 0) {  // (a 512-B read at a 512-B offset: accepted or EINVAL)
+        IndexFileFd fdirect(path, O_DIRECT);
+        uint32_t align = 4096;
+        if (fdirect.fd >= 0) {  // (a 512-B read at a 512-B offset: accepted or EINVAL)
             void* pb = nullptr;
             if (posix_memalign(&pb, 4096, 4096) == 0) {
-                if (::pread(home_fd_direct, pb, 512, 512) == 512) dio_align = 512;
+                if (::pread(fdirect.fd, pb, 512, 512) == 512) align = 512;
                 std::free(pb);
             }
         }
-        char magic[8];
-        uint32_t hdr[6] = {0, 0, 0, 0, 0, 0};
-        pread_all(magic, 8, 0);
-        const bool shard_file = std::memcmp(magic, "VDBIVS01", 8) == 0;  // (vdb_ivf_save of a sharded handle)
-        pread_all(hdr, shard_file ? 24 : 16, 8);
-        auto refuse = [&](const std::string& why) {
-            ::close(home_fd);
-            home_fd = -1;
-            if (home_fd_direct >= 0) ::close(home_fd_direct);
-            home_fd_direct = -1;
-            throw VdbError(VDB_ERR_INVALID_ARGUMENT, why);
-        };
-        if ((!shard_file && std::memcmp(magic, "VDBIVF01", 8) != 0) || hdr[0] != dim || hdr[1] != nlist ||
-            (int)hdr[2] != config_metric())
-            refuse("index file does not match this index's configuration");
-        if (shard_file && (hdr[4] == 0 || hdr[3] >= hdr[4])) refuse("shard file with an invalid (rank, world)");
-        const uint64_t hdr_bytes = shard_file ? 32 : 24;
+        IndexFileDirectory d;
+        index_file_checked([&] {
+            const IndexFileHeader hd = read_index_file_header(f, f.size);
+            require(!(hd.shard && unit_rows), "opening a shard file is not available with VDB_METRIC_COSINE_DISTANCE",
+                    VDB_ERR_UNSUPPORTED);
+            hd.require_config(dim, nlist, config_metric());
+            d = read_index_file_lists(hd, f, f.size);
+        });
         std::vector<float> c((size_t)nlist * dim);
-        pread_all(c.data(), c.size() * 4, hdr_bytes);
-        uint64_t at = hdr_bytes + (uint64_t)c.size() * 4;
-        std::vector<uint64_t> cnt(nlist, 0), stored(nlist, 0), off(nlist, 0);
-        for (uint32_t l = 0; l < nlist; ++l) {
-            uint64_t h2[2] = {0, 0};
-            pread_all(h2, shard_file ? 16 : 8, at);
-            cnt[l] = h2[0];
-            stored[l] = shard_file ? h2[1] : h2[0];
-            off[l] = at + (shard_file ? 16 : 8);
-            at = off[l] + stored[l] * 8 + stored[l] * (uint64_t)dim * 4;
-        }
-        std::vector<uint8_t> own(nlist, 1);
-        if (shard_file) {  // a list is this rank's when the file stores its rows (any plan)
-            for (uint32_t l = 0; l < nlist; ++l) {
-                if (stored[l] != 0 && stored[l] != cnt[l]) refuse("shard file stores part of a list");
-                own[l] = cnt[l] != 0 && stored[l] == cnt[l];
-            }
-        }
+        f(d.centroids_off, c.data(), d.centroid_bytes());
+        // accepted: the handle's old home goes (the locals close it), everything is replaced
+        std::swap(home_fd, f.fd);
+        std::swap(home_fd_direct, fdirect.fd);
+        dio_align = align;
+        file_bytes_read += f.bytes_read;
         HIPCHECK(hipMemcpy2DAsync(cent_rm.p, dp * 4, c.data(), dim * 4, dim * 4, nlist, hipMemcpyHostToDevice, stream));
         refresh_centroid_layout();
-        file_off = off;
-        count = cnt;
         total = 0;
-        for (uint32_t l = 0; l < nlist; ++l) total += cnt[l];
+        for (uint32_t l = 0; l < nlist; ++l) {
+            count[l] = d.lists[l].count;
+            owned[l] = d.owned(l);
+            total += count[l];
+        }
+        rank = d.header.rank;
+        world = d.header.world;
+        home = std::move(d);
         screen_ready = false;  // (everything is replaced: no arena rebuild for the old lists)
         arena_dropped = false;
         screen_sh.release();
@@ -1608,9 +1630,6 @@ struct vdb_ivf {
         arena_ids.release();
         arena_blocks = 0;
         block_off.assign(nlist, 0);
-        owned = own;
-        rank = shard_file ? hdr[3] : 0;
-        world = shard_file ? hdr[4] : 1;
         lc.reset(nlist, lc.capacity());
         upload_directory();
     }
@@ -1710,8 +1729,8 @@ struct vdb_ivf {
         if (c == 0) return;
         require(owned[l], "list is not stored on this shard", VDB_ERR_STATE);
         if (file_home()) {  // the file holds the list row-major, as returned
-            if (ids) pread_all(ids, c * 8, file_off[l]);
-            if (vectors) pread_all(vectors, c * dim * 4, file_off[l] + c * 8);
+            if (ids) pread_all(ids, c * 8, home.ids_offset(l, 0));
+            if (vectors) pread_all(vectors, c * dim * 4, home.row_offset(l, 0));
             return;
         }
         if (arena_dropped) {  // the row-major copy holds the list in slot (= add) order
