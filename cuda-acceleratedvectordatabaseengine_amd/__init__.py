@@ -145,6 +145,11 @@ def lib() -> ctypes.CDLL:
                                                          ctypes.POINTER(vp)]),
         "vdb_filter_create_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double),
                                                          ctypes.POINTER(ctypes.c_double)]),
+        "vdb_ivf_fetch_ids": (ctypes.c_int, [vp, vp, u64, vp, vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_fetch_ids_device": (ctypes.c_int, [vp, vp, u64, vp, vp, ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_search_ids": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp, vp]),
+        "vdb_fetch_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                 ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_ivf_search_device": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "vdb_ivf_set_shard": (ctypes.c_int, [vp, u32, u32]),
         "vdb_ivf_plan_shard": (ctypes.c_int, [vp, u32, u32, vp]),
@@ -490,6 +495,46 @@ class IVFFlatIndex:
         a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
         _check(lib().vdb_filter_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
         return {"mark_ms": a.value, "scan_ms": b.value, "merge_ms": c.value, "pairs_scanned": r.value}
+
+    def fetch_ids(self, ids):
+        """The stored rows carrying `ids` (vdb_ivf_fetch_ids; not in the reference). Returns
+        (vectors, found): vectors[i] is the row of ids[i] bit for bit as stored (the one at the
+        lowest (list, position) if the id is stored more than once), zeros with found[i] = 0
+        where no row carries it."""
+        i = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        n = i.shape[0]
+        V = np.empty((n, self.dimension), dtype=np.float32)
+        F = np.empty(n, dtype=np.uint8)
+        _check(lib().vdb_ivf_fetch_ids(self._h, _ptr(i), n, _ptr(V), _ptr(F), None))
+        return V, F
+
+    def fetch_ids_device(self, ids_ptr: int, n: int, vec_ptr: int | None = None, found_ptr: int | None = None) -> int:
+        """fetch_ids on buffers of the index's device that are complete before the call
+        (vdb_ivf_fetch_ids_device): n uint64 ids in, n x dimension floats and n bytes out, either
+        of which may be None. Returns the entries found."""
+        c = ctypes.c_uint64(0)
+        _check(lib().vdb_ivf_fetch_ids_device(self._h, ctypes.c_void_p(ids_ptr), n, ctypes.c_void_p(vec_ptr or 0),
+                                              ctypes.c_void_p(found_ptr or 0), ctypes.byref(c)))
+        return int(c.value)
+
+    def search_ids(self, ids, nprobe: int = 10, k: int = 10):
+        """search with the stored rows of `ids` as the queries (vdb_ivf_search_ids; not in the
+        reference); the rows never leave the device. Returns (distances, indices, found): the
+        found entries' results are search's over their rows in request order, the others hold
+        (FLT_MAX, UINT64_MAX)."""
+        i = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        n = i.shape[0]
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.uint64)
+        F = np.empty(n, dtype=np.uint8)
+        _check(lib().vdb_ivf_search_ids(self._h, _ptr(i), n, nprobe, k, _ptr(D), _ptr(I), _ptr(F)))
+        return D, I, F
+
+    def fetch_last_timing(self) -> dict:
+        """The calling thread's latest fetch_ids / search_ids by step (vdb_fetch_last_timing)."""
+        a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
+        _check(lib().vdb_fetch_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
+        return {"sort_ms": a.value, "locate_ms": b.value, "gather_ms": c.value, "rows_found": r.value}
 
     def prepare_filter(self, ids, include: bool = False, *, device_ptr: int | None = None, n: int = 0) -> Filter:
         """The id filter of search_filtered, prepared once (vdb_ivf_filter_create; not in the

@@ -4,6 +4,7 @@
 
 #include <cmath>
 
+#include "fetch.hpp"
 #include "filter.hpp"
 #include "filter_epoch.hpp"
 #include "prepared.hpp"
@@ -452,6 +453,49 @@ int vdb_filter_last_timing(double* mark_ms, double* scan_ms, double* merge_ms, u
     if (scan_ms) *scan_ms = g_filter_timing.scan_ms;
     if (merge_ms) *merge_ms = g_filter_timing.merge_ms;
     if (pairs_scanned) *pairs_scanned = g_filter_timing.pairs_scanned;
+    return VDB_OK;
+}
+
+static int fetch_entry(vdb_ivf* h, const uint64_t* ids, uint64_t n, float* vectors, uint8_t* found, uint64_t* n_found,
+                       bool device_bufs) {
+    return guarded([&] {
+        require(h != nullptr, "null handle");  // (before any device call)
+        require(ids || n == 0, "null ids");
+        require(n < (1ull << 31), "more than 2^31 - 1 ids in one fetch", VDB_ERR_UNSUPPORTED);
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        const uint64_t hits = fetch_ids(*h, ids, n, device_bufs, vectors, found);
+        if (n_found) *n_found = hits;
+    });
+}
+
+int vdb_ivf_fetch_ids(vdb_ivf* h, const uint64_t* ids, uint64_t n, float* vectors, uint8_t* found, uint64_t* n_found) {
+    return fetch_entry(h, ids, n, vectors, found, n_found, false);
+}
+
+int vdb_ivf_fetch_ids_device(vdb_ivf* h, const uint64_t* d_ids, uint64_t n, float* d_vectors, uint8_t* d_found,
+                             uint64_t* n_found) {
+    return fetch_entry(h, d_ids, n, d_vectors, d_found, n_found, true);
+}
+
+int vdb_ivf_search_ids(vdb_ivf* h, const uint64_t* ids, uint32_t n, uint32_t nprobe, uint32_t k, float* dist,
+                       uint64_t* result_ids, uint8_t* found) {
+    return guarded([&] {
+        require(h != nullptr, "null handle");  // (before any device call)
+        require(ids || n == 0, "null ids");
+        require(dist && result_ids, "null result buffer");
+        require(n < (1u << 31), "more than 2^31 - 1 ids in one search_ids", VDB_ERR_UNSUPPORTED);
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        search_ids(*h, ids, n, nprobe, k, dist, result_ids, found);
+    });
+}
+
+int vdb_fetch_last_timing(double* sort_ms, double* locate_ms, double* gather_ms, uint64_t* rows_found) {
+    if (sort_ms) *sort_ms = g_fetch_timing.sort_ms;
+    if (locate_ms) *locate_ms = g_fetch_timing.locate_ms;
+    if (gather_ms) *gather_ms = g_fetch_timing.gather_ms;
+    if (rows_found) *rows_found = g_fetch_timing.rows_found;
     return VDB_OK;
 }
 

@@ -67,6 +67,17 @@ void IVFFlatIndex::search_filtered(const float* queries, uint32_t n_queries, con
        "search_filtered");
 }
 
+uint64_t IVFFlatIndex::fetch(const uint64_t* ids, uint64_t n_ids, float* vectors, uint8_t* found) {
+    uint64_t n_found = 0;
+    ok(vdb_ivf_fetch_ids(h_, ids, n_ids, vectors, found, &n_found), "fetch");
+    return n_found;
+}
+
+void IVFFlatIndex::search_by_ids(const uint64_t* ids, uint32_t n_ids, const SearchParams& params, float* distances,
+                                 uint64_t* indices, uint8_t* found) {
+    ok(vdb_ivf_search_ids(h_, ids, n_ids, params.nprobe, params.k, distances, indices, found), "search_by_ids");
+}
+
 namespace {
 // The library's result into the caller's vectors, then released.
 void take_range_result(vdb_range_result* r, uint32_t n_queries, std::vector<uint64_t>& lims,

@@ -60,6 +60,15 @@ public:
     // id is not. The result is search()'s on an index holding only the allowed rows.
     void search_filtered(const float* queries, uint32_t n_queries, const SearchParams& params, const uint64_t* ids,
                          uint64_t n_ids, bool include, float* distances, uint64_t* indices);
+    // Not in the reference: the stored rows carrying the listed ids (vdb_ivf_fetch_ids), row i
+    // of vectors (n_ids x dimension) for ids[i], bit for bit as stored; zeros and found[i] = 0
+    // where no row carries it. vectors and found may each be null. Returns the entries found.
+    uint64_t fetch(const uint64_t* ids, uint64_t n_ids, float* vectors, uint8_t* found);
+    // Not in the reference: search() with the stored rows of the listed ids as the queries
+    // (vdb_ivf_search_ids); the rows never leave the device. The found entries' results are
+    // search()'s over their rows; the others hold (FLT_MAX, UINT64_MAX). found may be null.
+    void search_by_ids(const uint64_t* ids, uint32_t n_ids, const SearchParams& params, float* distances,
+                       uint64_t* indices, uint8_t* found);
     // Not in the reference: every stored row within `radius` of each query among the lists it
     // probes (vdb_ivf_range_search). Query i owns entries [lims[i], lims[i + 1]) of distances
     // and indices, ascending by (distance, id): search()'s entries for that query alone with

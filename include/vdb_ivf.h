@@ -333,6 +333,53 @@ int vdb_ivf_range_search_prepared(vdb_ivf* index, const vdb_filter* filter, cons
 /* Diagnostics: the calling thread's latest vdb_ivf_filter_create(_device) (HIP events): the
  * device sort of the ids, and the mark and count kernels. Either pointer may be NULL. */
 int vdb_filter_create_last_timing(double* sort_ms, double* mark_ms);
+/* Fetch by id: the stored rows that carry ids[0..n), and a search with stored rows as the
+ * queries. No counterpart in the reference; without it a row is only reachable through
+ * vdb_ivf_get_list over every list.
+ * vdb_ivf_fetch_ids, for request entry i: if a stored row carries ids[i], found[i] = 1 and
+ * vectors[i] holds its dim floats, bit for bit as vdb_ivf_get_list returns them (with
+ * VDB_METRIC_COSINE_DISTANCE the unit row as stored, not normalised again); otherwise found[i] =
+ * 0 and the row is dim zeros. An id stored more than once gives the row at the lowest list id
+ * and, within that list, the earliest position in add order. A repeat within ids[] gets the same
+ * row each time; the order of the request is kept. Pad slots are never matched, whatever ids[]
+ * holds, UINT64_MAX included. vectors (n x dim fp32), found (n bytes) and n_found may each be
+ * NULL (found alone: an existence check); *n_found counts entries, a repeated id every time it
+ * appears. n == 0 succeeds and touches no buffer. Host buffers.
+ * vdb_ivf_fetch_ids_device is the same on buffers of the handle's device that are complete
+ * before the call (n_found stays a host pointer).
+ * Nothing moves and nothing is rebuilt: the request is sorted on the device, one pass over the
+ * stored ids (8 bytes per stored row, no row data) finds each id's slot, and one wave per
+ * request entry copies its row from whichever fp32 layout the handle holds at that moment, the
+ * interleaved arena or the screen's row-major copy. Temporaries are the call's own:
+ * vdb_ivf_gpu_bytes_allocated is unchanged, prepared filters stay valid, no screen is built or
+ * dropped. The call holds the handle's lock and has finished its device work when it returns.
+ * vdb_ivf_search_ids: let F be the request entries that are found, in request order. Their
+ * result rows are, bit for bit, what vdb_ivf_search(index, rows of F, |F|, nprobe, k) returns
+ * (one call over the found rows only, so with stale_slots = 1 a slot's content passes from a found
+ * query to the next found query); entries that are not found get (FLT_MAX, UINT64_MAX) in every
+ * slot and found[i] = 0 (found may be NULL). The rows go from the gather's device buffer into
+ * the entry vdb_ivf_search_device uses, on the handle's stream, and never leave the device;
+ * every route serves them as it serves any device query (the screen, the exact scan, k > 64,
+ * the run-time floor), and a VDB_METRIC_COSINE_DISTANCE handle normalises them like any query.
+ * Like any search, this one may build the screen. Host buffers.
+ * Limits of this version (the handle is untouched by a refusal): a null handle, null ids with
+ * n > 0, and null distances or result_ids give VDB_ERR_INVALID_ARGUMENT; n >= 2^31, k or nprobe
+ * above 1024, a handle in the list-cache tier (option list_cache_bytes, or max_gpu_memory
+ * exceeded), a file-home handle (vdb_ivf_open_lists), a sharded handle (world > 1) and a group
+ * handle give VDB_ERR_UNSUPPORTED: the set vdb_ivf_search_filtered refuses, for the same reasons
+ * (the rows are not all in this device's HBM). Not offered yet: those four kinds of handle, the
+ * gRPC service, a caller's stream for the device variant, coalescing of concurrent fetches. */
+int vdb_ivf_fetch_ids(vdb_ivf* index, const uint64_t* ids, uint64_t n,
+                      float* vectors, uint8_t* found, uint64_t* n_found);
+int vdb_ivf_fetch_ids_device(vdb_ivf* index, const uint64_t* d_ids, uint64_t n,
+                             float* d_vectors, uint8_t* d_found, uint64_t* n_found);
+int vdb_ivf_search_ids(vdb_ivf* index, const uint64_t* ids, uint32_t n, uint32_t nprobe, uint32_t k,
+                       float* distances, uint64_t* result_ids, uint8_t* found);
+/* Diagnostics: the calling thread's latest vdb_ivf_fetch_ids(_device) or vdb_ivf_search_ids, by
+ * step (HIP events): the device sort of the request, the locate pass, the gather (search_ids:
+ * its two passes, the marks and then the found rows), and the entries found. Any pointer may be
+ * NULL; a thread without a call reads zeros. */
+int vdb_fetch_last_timing(double* sort_ms, double* locate_ms, double* gather_ms, uint64_t* rows_found);
 /* Persist / restore centroids and lists (IVFFlatIndex::save/load, engine/ivf_flat_index.h:66-67,
  * declared but never defined in the reference; this engine's own file format). */
 int vdb_ivf_save(vdb_ivf* index, const char* path);
