@@ -121,6 +121,13 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_remove_ids": (ctypes.c_int, [vp, vp, u64, ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_remove_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_upsert": (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(ctypes.c_uint64),
+                                          ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_upsert_device": (ctypes.c_int, [vp, vp, vp, u64, ctypes.POINTER(ctypes.c_uint64),
+                                                 ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_upsert_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                  ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_ivf_search": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp]),
         "vdb_ivf_search_filtered": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, u64, ctypes.c_int, vp, vp]),
         "vdb_filter_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
@@ -439,6 +446,36 @@ class IVFFlatIndex:
         a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
         _check(lib().vdb_remove_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
         return {"mark_ms": a.value, "plan_ms": b.value, "compact_ms": c.value, "rows_kept": r.value}
+
+    def upsert(self, vectors: np.ndarray, ids: np.ndarray):
+        """Replace the rows of the listed ids that are stored and insert the others, in one pass
+        over the lists (vdb_ivf_upsert; not in the reference). An id listed more than once takes
+        its last entry. Returns (replaced, inserted): stored rows that went, distinct ids. The
+        index is afterwards the one remove_ids(ids) followed by add(those entries) leaves."""
+        v = np.ascontiguousarray(vectors, dtype=np.float32).reshape(-1, self.dimension)
+        i = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        if i.shape[0] != v.shape[0]:
+            raise ValueError("vectors and ids differ in length")
+        r, w = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().vdb_ivf_upsert(self._h, _ptr(v), _ptr(i), v.shape[0], ctypes.byref(r), ctypes.byref(w)))
+        return int(r.value), int(w.value)
+
+    def upsert_device(self, vec_ptr: int, ids_ptr: int, n: int):
+        """upsert on buffers of the index's device that are complete before the call
+        (vdb_ivf_upsert_device): n x dimension floats and n uint64 ids. Returns (replaced, inserted)."""
+        r, w = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().vdb_ivf_upsert_device(self._h, ctypes.c_void_p(vec_ptr), ctypes.c_void_p(ids_ptr), n,
+                                           ctypes.byref(r), ctypes.byref(w)))
+        return int(r.value), int(w.value)
+
+    def upsert_last_timing(self) -> dict:
+        """The calling thread's latest upsert by step (vdb_upsert_last_timing)."""
+        a, b, c, d = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        k, w = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().vdb_upsert_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d),
+                                            ctypes.byref(k), ctypes.byref(w)))
+        return {"resolve_ms": a.value, "mark_ms": b.value, "plan_ms": c.value, "move_ms": d.value,
+                "rows_kept": k.value, "rows_written": w.value}
 
     def assign_device(self, vec_ptr: int, n: int, lists_ptr: int):
         """Exact nearest-centroid list of n device rows into u32 lists_ptr (assign_to_lists, cpp:259-295)."""

@@ -11,6 +11,7 @@
 #include "range.hpp"
 #include "remove.hpp"
 #include "remove_plan.hpp"
+#include "upsert.hpp"
 
 namespace vdbe {
 thread_local std::string g_last_error;
@@ -271,6 +272,71 @@ int vdb_remove_last_timing(double* mark_ms, double* plan_ms, double* compact_ms,
     if (plan_ms) *plan_ms = g_remove_timing.plan_ms;
     if (compact_ms) *compact_ms = g_remove_timing.compact_ms;
     if (rows_kept) *rows_kept = g_remove_timing.rows_kept;
+    return VDB_OK;
+}
+
+namespace vdbe {
+// The refusals of vdb_ivf_upsert(_device), in the header's order, under the handle's lock. A
+// refusal leaves the handle, and so its prepared filters, untouched.
+inline void upsert_refusals(const vdb_ivf* h) {
+    require(!h->file_home(), "lists are served from a file (vdb_ivf_open_lists): the index is read-only",
+            VDB_ERR_STATE);
+    // A rank cannot see ids in lists it does not store, and the ranks' list sizes must stay
+    // equal for attach_comm: remove's reason.
+    require(h->is_group() || (h->world == 1 && h->comm_world == 1),
+            "upsert is not available on a sharded handle (set_shard / plan_shard / a shard file / "
+            "attach_comm with world > 1)",
+            VDB_ERR_UNSUPPORTED);
+    no_group(h, "upsert");
+}
+}  // namespace vdbe
+
+int vdb_ivf_upsert(vdb_ivf* h, const float* v, const uint64_t* ids, uint64_t n, uint64_t* replaced,
+                   uint64_t* inserted) {
+    return guarded([&] {
+        require(h && ((v && ids) || n == 0), "null argument");  // (before any device call)
+        if (replaced) *replaced = 0;
+        if (inserted) *inserted = 0;
+        require(n < (1ull << 31), "more than 2^31 - 1 entries in one upsert", VDB_ERR_UNSUPPORTED);
+        std::lock_guard<std::mutex> g(h->mu);
+        upsert_refusals(h);
+        h->set_device();
+        g_upsert_timing = UpsertTiming{};
+        if (n == 0) return;
+        rows_may_move(h);
+        DevBuf<float> dv;
+        DevBuf<uint64_t> di;
+        HIPCHECK(hipMemcpyAsync(dv.ensure(n * h->dim), v, n * h->dim * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(di.ensure(n), ids, n * 8, hipMemcpyHostToDevice, h->stream));
+        upsert(*h, dv.p, di.p, n, replaced, inserted);
+    });
+}
+
+int vdb_ivf_upsert_device(vdb_ivf* h, const float* d_v, const uint64_t* d_ids, uint64_t n, uint64_t* replaced,
+                          uint64_t* inserted) {
+    return guarded([&] {
+        require(h && ((d_v && d_ids) || n == 0), "null argument");  // (before any device call)
+        if (replaced) *replaced = 0;
+        if (inserted) *inserted = 0;
+        require(n < (1ull << 31), "more than 2^31 - 1 entries in one upsert", VDB_ERR_UNSUPPORTED);
+        std::lock_guard<std::mutex> g(h->mu);
+        upsert_refusals(h);
+        h->set_device();
+        g_upsert_timing = UpsertTiming{};
+        if (n == 0) return;
+        rows_may_move(h);
+        upsert(*h, d_v, d_ids, n, replaced, inserted);
+    });
+}
+
+int vdb_upsert_last_timing(double* resolve_ms, double* mark_ms, double* plan_ms, double* move_ms, uint64_t* rows_kept,
+                           uint64_t* rows_written) {
+    if (resolve_ms) *resolve_ms = g_upsert_timing.resolve_ms;
+    if (mark_ms) *mark_ms = g_upsert_timing.mark_ms;
+    if (plan_ms) *plan_ms = g_upsert_timing.plan_ms;
+    if (move_ms) *move_ms = g_upsert_timing.move_ms;
+    if (rows_kept) *rows_kept = g_upsert_timing.rows_kept;
+    if (rows_written) *rows_written = g_upsert_timing.rows_written;
     return VDB_OK;
 }
 

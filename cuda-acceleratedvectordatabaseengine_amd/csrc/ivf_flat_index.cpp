@@ -54,6 +54,11 @@ uint64_t IVFFlatIndex::remove(const uint64_t* ids, uint64_t n_ids) {
     return removed;
 }
 
+void IVFFlatIndex::upsert(const float* vectors, const uint64_t* ids, uint64_t n_vectors, uint64_t* replaced,
+                          uint64_t* inserted) {
+    ok(vdb_ivf_upsert(h_, vectors, ids, n_vectors, replaced, inserted), "upsert");
+}
+
 void IVFFlatIndex::search(const float* queries, uint32_t n_queries, const SearchParams& params, float* distances,
                           uint64_t* indices) {
     ok(vdb_ivf_search(h_, queries, n_queries, params.nprobe, params.k, distances, indices), "search");

@@ -11,8 +11,8 @@
 //
 // A free function over vdb_ivf's public members, and not a member next to relayout(): the
 // handle's header is one of the sources the build id hashes, and this feature touches no scan
-// kernel. The price is that the fresh arena's allocation below repeats about 30 lines of
-// vdb_ivf::relayout (engine.hpp) — keep the two in step.
+// kernel. The price is that fresh_arena below repeats the allocation of vdb_ivf::relayout
+// (engine.hpp) — keep the two in step. upsert.cpp calls it too.
 #include "remove.hpp"
 
 #include <chrono>
@@ -43,6 +43,17 @@ struct TimedEvents {
 };
 
 }  // namespace
+
+void fresh_arena(vdb_ivf& h, uint64_t blocks, DevBuf<float4>& rows, DevBuf<uint64_t>& ids) {
+    const bool host_arena = h.arena.host;
+    rows.pooled = ids.pooled = !host_arena && VDB_DEVICE_POOL;
+    rows.host = ids.host = host_arena;
+    const size_t vec4 = (size_t)(blocks + 1) * h.d4 * 64;
+    rows.ensure(vec4);
+    ids.ensure((size_t)(blocks + 1) * 64);
+    HIPCHECK(hipMemsetAsync(rows.p, 0, vec4 * sizeof(float4), h.stream));
+    HIPCHECK(hipMemsetAsync(ids.p, 0xFF, (size_t)(blocks + 1) * 64 * 8, h.stream));
+}
 
 uint64_t remove_ids(vdb_ivf& h, const std::vector<uint64_t>& sorted, std::vector<uint64_t>* per_list) {
     require(!h.file_home(), "lists are served from a file (vdb_ivf_open_lists): the index is read-only",
@@ -94,19 +105,11 @@ uint64_t remove_ids(vdb_ivf& h, const std::vector<uint64_t>& sorted, std::vector
         if (h.block_off != off0 || h.arena_blocks != nb0) mark_and_plan();
     }
 
-    // the fresh arena, allocated and cleared as in vdb_ivf::relayout: rows zero, ids 0xFF, one
-    // slack block past the last list (the scan prefetches one chunk and one block of ids
-    // beyond the segment it streams). The old arena is swapped out only once this one is whole.
-    const bool host_arena = h.arena.host;
+    // the fresh arena; the old one is swapped out only once this one is whole
     const uint64_t blocks = plan.new_blocks;
-    DevBuf<float4> na{!host_arena};
-    DevBuf<uint64_t> ni{!host_arena};
-    na.host = ni.host = host_arena;
-    const size_t vec4 = (size_t)(blocks + 1) * h.d4 * 64;
-    na.ensure(vec4);
-    ni.ensure((size_t)(blocks + 1) * 64);
-    HIPCHECK(hipMemsetAsync(na.p, 0, vec4 * sizeof(float4), s));
-    HIPCHECK(hipMemsetAsync(ni.p, 0xFF, (size_t)(blocks + 1) * 64 * 8, s));
+    DevBuf<float4> na;
+    DevBuf<uint64_t> ni;
+    fresh_arena(h, blocks, na, ni);
     DevBuf<uint64_t> d_base;
     HIPCHECK(hipMemcpyAsync(d_base.ensure(plan.base.size()), plan.base.data(), plan.base.size() * 8,
                             hipMemcpyHostToDevice, s));

@@ -21,4 +21,12 @@ extern thread_local RemoveTiming g_remove_timing;
 // untouched. Not for sharded handles: the caller refuses those (a group calls it per member).
 uint64_t remove_ids(vdb_ivf& h, const std::vector<uint64_t>& sorted, std::vector<uint64_t>* per_list);
 
+// A fresh, cleared list arena of `blocks` blocks for h in the caller's two empty buffers, where
+// h's arena lives (HBM, or page-locked host memory in the list-cache tier), as
+// vdb_ivf::relayout allocates it: rows zero, ids 0xFF, one slack block past the last list (the
+// scan prefetches one chunk and one block of ids beyond the segment it streams). The clears are
+// queued on h.stream. h is not touched: the caller swaps the pair in once it is whole
+// (remove.cpp, upsert.cpp).
+void fresh_arena(vdb_ivf& h, uint64_t blocks, DevBuf<float4>& rows, DevBuf<uint64_t>& ids);
+
 }  // namespace vdbe

@@ -9,7 +9,8 @@
 namespace vdbk {
 
 // keepmask[b] bit i = slot i of block b holds a row (i < valid[b]) whose id is not one of
-// sorted[0..n) (ascending, each once). Reads the ids only (8 bytes per slot).
+// sorted[0..n) (ascending; repeats do no harm, the lookup is a lower bound: remove passes each
+// id once, upsert the whole request as sorted). Reads the ids only (8 bytes per slot).
 void launch_remove_mark(const uint64_t* arena_ids, const uint32_t* valid, uint64_t nblocks, const uint64_t* sorted,
                         uint32_t n, unsigned long long* keepmask, hipStream_t s);
 

@@ -53,6 +53,12 @@ public:
     // (vdb_ivf_remove_ids) and returns how many went; the index is afterwards the one built
     // by adding the surviving rows in their original order.
     uint64_t remove(const uint64_t* ids, uint64_t n_ids);
+    // Not in the reference: replaces the rows of the listed ids that are stored and inserts the
+    // others in one pass over the lists (vdb_ivf_upsert). An id listed more than once takes its
+    // last entry; the index is afterwards the one remove(ids) followed by add(those entries)
+    // leaves. replaced: stored rows that went; inserted: distinct ids. Either may be null.
+    void upsert(const float* vectors, const uint64_t* ids, uint64_t n_vectors, uint64_t* replaced = nullptr,
+                uint64_t* inserted = nullptr);
     void search(const float* queries, uint32_t n_queries, const SearchParams& params, float* distances,
                 uint64_t* indices);
     // Not in the reference: search over the stored rows the id filter allows

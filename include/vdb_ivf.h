@@ -205,6 +205,54 @@ int vdb_ivf_remove_ids(vdb_ivf* index, const uint64_t* ids, uint64_t n, uint64_t
  * step: the mark kernel and the compact kernel (HIP events), the host plan between them, and
  * the rows the compact pass moved. Any pointer may be NULL. */
 int vdb_remove_last_timing(double* mark_ms, double* plan_ms, double* compact_ms, uint64_t* rows_kept);
+/* Upsert: replace the rows of ids that are stored and insert the others, in one call. No
+ * counterpart in the reference (it can neither delete nor change a row).
+ * Winners: the winners W of a request are, for every distinct id in ids[0..n), the entry with
+ * the largest index carrying it (last write wins); W stays in request order.
+ * After the call the handle is indistinguishable from the same handle after
+ * vdb_ivf_remove_ids(all request ids) followed by vdb_ivf_add(rows of W, ids of W): totals, list
+ * sizes, every list's ids and row bits in vdb_ivf_get_list order, and every search result. So:
+ * every stored copy of a listed id goes (an index may hold an id more than once); survivors
+ * keep their order in each list; each winner is assigned by the exact nearest-centroid
+ * assignment of add and appended after its list's survivors, in request order; a row whose new
+ * vector lands in the list it was in still moves to that list's end. Centroids do not change; a
+ * list may become empty. No id value is special, and pad slots are never matched.
+ * *replaced receives the number of stored rows removed, *inserted |W|; either may be NULL. With
+ * VDB_METRIC_COSINE_DISTANCE the winners are normalised once, as add normalises them.
+ * n == 0 succeeds and leaves the handle untouched (prepared filters stay live,
+ * vdb_ivf_gpu_bytes_allocated is unchanged). A request none of whose ids is stored is exactly an
+ * add of W, as is any request on a trained, empty index. Any call with n > 0 makes the handle's
+ * prepared filters stale. Searches in flight are quiesced first, as by add, and the next search
+ * rebuilds the screen; the call holds the handle's lock and has finished its device work when it
+ * returns.
+ * The request is resolved on the device (a stable sort of (id, position), the winners marked
+ * and packed densely), and the lists are rebuilt once: the survivors are compacted into one
+ * fresh arena sized for survivors and winners, and the winners scattered behind them (peak
+ * memory old arena + that arena; the sequence of the two calls allocates and fills an arena
+ * twice). The rows never travel through the host after the host variant's upload.
+ * vdb_ivf_upsert_device is the same on buffers of the handle's device that are complete before
+ * the call (replaced and inserted stay host pointers).
+ * The list-cache tier with its home in host memory is served as remove serves it: an upsert that
+ * grows the lists past max_gpu_memory switches the handle into the tier, one that shrinks them
+ * below the cap brings them back.
+ * Refusals leave the handle untouched: a null handle, or null vectors / ids with n > 0, give
+ * VDB_ERR_INVALID_ARGUMENT before any device call; n >= 2^31 VDB_ERR_UNSUPPORTED; lists served
+ * from a file (vdb_ivf_open_lists) VDB_ERR_STATE, read-only as for add; a sharded handle (world >
+ * 1 by any route) VDB_ERR_UNSUPPORTED, for remove's reason; a group handle VDB_ERR_UNSUPPORTED. An
+ * untrained handle gets what vdb_ivf_add gives it. If the fresh arena cannot be allocated:
+ * VDB_ERR_OUT_OF_MEMORY, the lists unchanged. Not offered yet: a group handle, the gRPC service,
+ * a caller's stream for the device variant. */
+int vdb_ivf_upsert(vdb_ivf* index, const float* vectors, const uint64_t* ids, uint64_t n,
+                   uint64_t* replaced, uint64_t* inserted);
+int vdb_ivf_upsert_device(vdb_ivf* index, const float* d_vectors, const uint64_t* d_ids, uint64_t n,
+                          uint64_t* replaced, uint64_t* inserted);
+/* Diagnostics: the calling thread's latest vdb_ivf_upsert(_device), by step: the resolution of
+ * the request (sort, winners, pack), the mark kernel, and the move (the compact of the survivors
+ * and the scatter of the winners) by HIP events, the host plan between them, the stored rows the
+ * compact moved and the winners written. Any pointer may be NULL; a thread without a call, and a
+ * call with n == 0, read zeros. */
+int vdb_upsert_last_timing(double* resolve_ms, double* mark_ms, double* plan_ms, double* move_ms,
+                           uint64_t* rows_kept, uint64_t* rows_written);
 /* Filtered search: vdb_ivf_search over the stored rows an id filter allows. filter_ids[0..
  * n_filter) is a host array in any order; repeats and ids that are not stored are ignored.
  * VDB_FILTER_EXCLUDE: a stored row is allowed unless its id is listed (tombstones: n_filter
@@ -300,7 +348,7 @@ int vdb_range_last_timing(double* scan_ms, double* order_ms, uint64_t* pairs_sca
  * A filter describes the handle's rows where they lay when it was made. It stays valid across
  * searches of every kind, including the switch between the lists' two fp32 layouts; it is stale
  * once a call has run that can move a row: vdb_ivf_add*, a vdb_ivf_remove_ids that removed a
- * row, vdb_ivf_load, vdb_ivf_open_lists, vdb_ivf_set_shard* / vdb_ivf_plan_shard*,
+ * row, a vdb_ivf_upsert* with n > 0, vdb_ivf_load, vdb_ivf_open_lists, vdb_ivf_set_shard* / vdb_ivf_plan_shard*,
  * vdb_ivf_set_option of list_cache_bytes or max_gpu_memory, and vdb_ivf_destroy. A stale filter
  * is refused with VDB_ERR_STATE by every call that takes one; vdb_filter_stale tells (1 also for
  * NULL), and vdb_filter_free releases it, before or after the handle was destroyed.
