@@ -150,6 +150,12 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, vp]),
         "vdb_ivf_range_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, ctypes.c_float, u64,
                                                          ctypes.POINTER(vp)]),
+        "vdb_ivf_range_search_screened": (ctypes.c_int, [vp, vp, vp, u32, u32, ctypes.c_float, u64,
+                                                         ctypes.POINTER(vp)]),
+        "vdb_range_screen_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64),
+                                                        ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
+                                                        ctypes.POINTER(ctypes.c_uint32)]),
         "vdb_filter_create_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double),
                                                          ctypes.POINTER(ctypes.c_double)]),
         "vdb_ivf_fetch_ids": (ctypes.c_int, [vp, vp, u64, vp, vp, ctypes.POINTER(ctypes.c_uint64)]),
@@ -608,27 +614,36 @@ class IVFFlatIndex:
         return D, I
 
     def range_search_prepared(self, queries: np.ndarray, flt: "Filter | None", radius: float, *, nprobe: int = 10,
-                              reserve: int = 0):
+                              reserve: int = 0, screen: bool = False):
         """range_search over the rows the filter allows (vdb_ivf_range_search_prepared): the
         result range_search gives on an index holding only those rows. flt=None: range_search.
-        Returns (lims, distances, ids)."""
+        screen: as for range_search. Returns (lims, distances, ids)."""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
         r = ctypes.c_void_p()
-        _check(lib().vdb_ivf_range_search_prepared(self._h, flt._f if flt is not None else None, _ptr(q), q.shape[0],
-                                                   nprobe, float(radius), reserve, ctypes.byref(r)))
+        call = lib().vdb_ivf_range_search_screened if screen else lib().vdb_ivf_range_search_prepared
+        _check(call(self._h, flt._f if flt is not None else None, _ptr(q), q.shape[0], nprobe, float(radius), reserve,
+                    ctypes.byref(r)))
         return self._take_range_result(r, q.shape[0])
 
-    def range_search(self, queries: np.ndarray, radius: float, *, nprobe: int = 10, reserve: int = 0):
+    def range_search(self, queries: np.ndarray, radius: float, *, nprobe: int = 10, reserve: int = 0,
+                     screen: bool = False):
         """Every stored row within `radius` of each query among the lists it probes
         (vdb_ivf_range_search; not in the reference). Returns (lims, distances, ids): query i
         owns entries [lims[i], lims[i + 1]), ascending by (distance, id) — search's entries for
         that query alone with d <= radius, however many there are. reserve: entries of the
-        device hit buffer a batch starts with (0: automatic)."""
+        device hit buffer a batch starts with (0: automatic). screen=True serves the call through
+        the screen the index holds at that moment (vdb_ivf_range_search_screened): the same
+        result bit for bit, from a quarter or half of the bytes; without a live screen the exact
+        scan serves."""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
         n = q.shape[0]
         L = lib()
         r = ctypes.c_void_p()
-        _check(L.vdb_ivf_range_search(self._h, _ptr(q), n, nprobe, float(radius), reserve, ctypes.byref(r)))
+        if screen:
+            _check(L.vdb_ivf_range_search_screened(self._h, None, _ptr(q), n, nprobe, float(radius), reserve,
+                                                   ctypes.byref(r)))
+        else:
+            _check(L.vdb_ivf_range_search(self._h, _ptr(q), n, nprobe, float(radius), reserve, ctypes.byref(r)))
         return self._take_range_result(r, n)
 
     @staticmethod
@@ -657,6 +672,16 @@ class IVFFlatIndex:
         _check(lib().vdb_range_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(p), ctypes.byref(h),
                                            ctypes.byref(r)))
         return {"scan_ms": a.value, "order_ms": b.value, "pairs_scanned": p.value, "hits": h.value, "reruns": r.value}
+
+    def range_screen_last_timing(self) -> dict:
+        """The calling thread's latest range_search(..., screen=True) by step (vdb_range_screen_last_timing)."""
+        a, b, c = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        p, m = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        sb, eb = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib().vdb_range_screen_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(p),
+                                                  ctypes.byref(m), ctypes.byref(sb), ctypes.byref(eb)))
+        return {"pairs_ms": a.value, "bound_ms": b.value, "recheck_ms": c.value, "pairs_bounded": p.value,
+                "candidates": m.value, "screened_batches": sb.value, "exact_batches": eb.value}
 
     def search_device(self, q_ptr: int, n: int, nprobe: int, k: int, d_ptr: int, i_ptr: int,
                       stream: int | None = None):

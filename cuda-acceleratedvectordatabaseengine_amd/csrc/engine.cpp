@@ -662,6 +662,30 @@ int vdb_ivf_range_search_prepared(vdb_ivf* h, const vdb_filter* f, const float* 
     });
 }
 
+int vdb_ivf_range_search_screened(vdb_ivf* h, const vdb_filter* f, const float* q, uint32_t n, uint32_t nprobe,
+                                  float radius, uint64_t reserve, vdb_range_result** out) {
+    return guarded([&] {
+        require(h && (q || n == 0) && out, "null argument");  // (a null filter: the unfiltered call)
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        *out = (f ? range_search_prepared(*h, *f, q, n, nprobe, radius, reserve, true)
+                  : range_search(*h, q, n, nprobe, radius, reserve, nullptr, nullptr, true))
+                   .release();
+    });
+}
+
+int vdb_range_screen_last_timing(double* pairs_ms, double* bound_ms, double* recheck_ms, uint64_t* pairs_bounded,
+                                 uint64_t* candidates, uint32_t* screened_batches, uint32_t* exact_batches) {
+    if (pairs_ms) *pairs_ms = g_range_screen_timing.pairs_ms;
+    if (bound_ms) *bound_ms = g_range_screen_timing.bound_ms;
+    if (recheck_ms) *recheck_ms = g_range_screen_timing.recheck_ms;
+    if (pairs_bounded) *pairs_bounded = g_range_screen_timing.pairs_bounded;
+    if (candidates) *candidates = g_range_screen_timing.candidates;
+    if (screened_batches) *screened_batches = g_range_screen_timing.screened_batches;
+    if (exact_batches) *exact_batches = g_range_screen_timing.exact_batches;
+    return VDB_OK;
+}
+
 int vdb_filter_create_last_timing(double* sort_ms, double* mark_ms) {
     if (sort_ms) *sort_ms = g_filter_create_timing.sort_ms;
     if (mark_ms) *mark_ms = g_filter_create_timing.mark_ms;

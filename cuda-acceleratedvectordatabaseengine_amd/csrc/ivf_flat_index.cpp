@@ -144,6 +144,16 @@ void IVFFlatIndex::range_search_prepared(const float* queries, uint32_t n_querie
     take_range_result(r, n_queries, lims, distances, indices);
 }
 
+void IVFFlatIndex::range_search_screened(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
+                                         const Filter* filter, std::vector<uint64_t>& lims,
+                                         std::vector<float>& distances, std::vector<uint64_t>& indices) {
+    if (filter && !filter->handle()) throw std::invalid_argument("range_search_screened: an empty Filter");
+    vdb_range_result* r = nullptr;
+    ok(vdb_ivf_range_search_screened(h_, filter ? filter->handle() : nullptr, queries, n_queries, nprobe, radius, 0, &r),
+       "range_search_screened");
+    take_range_result(r, n_queries, lims, distances, indices);
+}
+
 void IVFFlatIndex::search_batch(const std::vector<float*>& queries, const std::vector<SearchParams>& params,
                                 std::vector<float*>& distances, std::vector<uint64_t*>& indices) {
     if (params.size() != queries.size() || distances.size() != queries.size() || indices.size() != queries.size())

@@ -170,12 +170,13 @@ void search_prepared(vdb_ivf& h, const vdb_filter& f, const float* queries, uint
 }
 
 std::unique_ptr<vdb_range_result> range_search_prepared(vdb_ivf& h, const vdb_filter& f, const float* queries,
-                                                        uint32_t n, uint32_t nprobe, float radius, uint64_t reserve) {
+                                                        uint32_t n, uint32_t nprobe, float radius, uint64_t reserve,
+                                                        bool screen) {
     require_filter(h, f);
     require(!std::isnan(radius), "the radius is NaN");
     require_resident_single(h, "range_search_prepared");
     require_live(f);
-    return range_search(h, queries, n, nprobe, radius, reserve, f.allow.p, f.allowed.p);
+    return range_search(h, queries, n, nprobe, radius, reserve, f.allow.p, f.allowed.p, screen);
 }
 
 }  // namespace vdbe

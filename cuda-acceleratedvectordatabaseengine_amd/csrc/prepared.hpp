@@ -53,6 +53,7 @@ std::unique_ptr<vdb_filter> filter_combine(const vdb_filter& a, const vdb_filter
 void search_prepared(vdb_ivf& h, const vdb_filter& f, const float* queries, uint32_t n, uint32_t nprobe, uint32_t k,
                      float* distances, uint64_t* ids);
 std::unique_ptr<vdb_range_result> range_search_prepared(vdb_ivf& h, const vdb_filter& f, const float* queries,
-                                                        uint32_t n, uint32_t nprobe, float radius, uint64_t reserve);
+                                                        uint32_t n, uint32_t nprobe, float radius, uint64_t reserve,
+                                                        bool screen = false);
 
 }  // namespace vdbe

@@ -110,6 +110,11 @@ public:
     void range_search_prepared(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
                                const Filter& filter, std::vector<uint64_t>& lims, std::vector<float>& distances,
                                std::vector<uint64_t>& indices);
+    // range_search (filter == nullptr) or range_search_prepared served through the screen the
+    // index holds at that moment (vdb_ivf_range_search_screened): the same result, bit for bit.
+    void range_search_screened(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
+                               const Filter* filter, std::vector<uint64_t>& lims, std::vector<float>& distances,
+                               std::vector<uint64_t>& indices);
     // Declared but never defined in the reference: here request i searches the single
     // query queries[i] with params[i] into distances[i] / indices[i] (params[i].k slots).
     void search_batch(const std::vector<float*>& queries, const std::vector<SearchParams>& params,

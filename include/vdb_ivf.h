@@ -315,8 +315,9 @@ int vdb_filter_last_timing(double* mark_ms, double* scan_ms, double* merge_ms, u
  * and a NaN radius give VDB_ERR_INVALID_ARGUMENT; a handle in the list-cache tier, a file-home
  * handle, a sharded handle and a group handle give VDB_ERR_UNSUPPORTED, as does a batch with
  * more than 2^31 - 1 hits (lower the `batch` option). A filter combined with a radius is
- * vdb_ivf_range_search_prepared (below). Not offered yet: a screened range scan, per-query
- * radii, a device-pointer variant, the gRPC service, coalescing of concurrent range calls. */
+ * vdb_ivf_range_search_prepared, the same result through the screen vdb_ivf_range_search_screened
+ * (both below). Not offered yet: per-query radii, a device-pointer variant, the gRPC service,
+ * coalescing of concurrent range calls. */
 typedef struct vdb_range_result vdb_range_result;
 int vdb_ivf_range_search(vdb_ivf* index, const float* queries, uint32_t n, uint32_t nprobe, float radius,
                          uint64_t reserve, vdb_range_result** out);
@@ -378,6 +379,47 @@ int vdb_ivf_search_prepared(vdb_ivf* index, const vdb_filter* filter, const floa
                             uint32_t nprobe, uint32_t k, float* distances, uint64_t* ids);
 int vdb_ivf_range_search_prepared(vdb_ivf* index, const vdb_filter* filter, const float* queries, uint32_t n,
                                   uint32_t nprobe, float radius, uint64_t reserve, vdb_range_result** out);
+/* Range search through the screen: vdb_ivf_range_search (filter == NULL) or
+ * vdb_ivf_range_search_prepared served from the shadow the screened search keeps. The result is,
+ * bit for bit (lims, ids, distance bits), what the exact call returns, with its reserve, its
+ * re-run and its independence of stale_slots and batch; only the bytes read differ.
+ * Per batch the pairs are grouped sixteen to an item, the screened search's own pairs kernel
+ * prepares them, a bound kernel computes the screen's lower bound of every (query, row) pair on
+ * the matrix cores from the int8 or bf16 shadow (a quarter or half of the fp32 bytes) and keeps
+ * the pairs whose bound is not above the radius, and a re-check computes exactly those pairs'
+ * sequential fp32 distances from the row-major copy; the hits are ordered as the exact call
+ * orders them. A huge or non-finite row, query or centroid has no finite bound and is always
+ * re-checked. With a filter, a block of 64 slots without an allowed row is skipped unread.
+ * Routing: the call uses the screen the handle holds at that moment and builds, refreshes and
+ * releases nothing (vdb_ivf_gpu_bytes_allocated is the same before and after, prepared filters
+ * stay live). A handle without a live screen (before its first search, after an add, remove,
+ * upsert or new centroids until the next search, with the option screen 0, with
+ * VDB_METRIC_COSINE) is served by the exact path, unchanged. L2, inner product and
+ * VDB_METRIC_COSINE_DISTANCE (thresholded and mapped as the exact call does) go through the
+ * screen.
+ * Fallback: a batch's candidate buffer holds 4 entries (8 bytes each) per entry of its hit
+ * buffer, so 1,048,576 at reserve == 0, and at most 2^28. A batch whose bound keeps more than
+ * that is served by the exact scan instead (a radius that wide is the exact scan's work); a
+ * batch whose hits exceed the hit buffer runs its re-check once more, the candidates kept.
+ * Refusals are those of vdb_ivf_range_search(_prepared), the handle untouched and *out written
+ * on success only: a null handle, queries or out and a NaN radius VDB_ERR_INVALID_ARGUMENT, as
+ * a filter of another handle; the list-cache tier, a file-home, a sharded and a group handle
+ * VDB_ERR_UNSUPPORTED; a stale filter VDB_ERR_STATE. The call holds the handle's lock and has
+ * finished its device work when it returns.
+ * vdb_range_last_timing reports this call too: scan_ms covers grouping, pairs, bound and
+ * re-check (or the exact scan of a batch that fell back), pairs_scanned the exact distances
+ * computed (the re-checked candidates, and every pair of a batch that fell back).
+ * Not offered: the list-cache tier, group and sharded handles, per-query radii, a device-pointer
+ * variant, the gRPC service; vdb_ivf_range_search(_prepared) keep the exact route. */
+int vdb_ivf_range_search_screened(vdb_ivf* index, const vdb_filter* filter, const float* queries, uint32_t n,
+                                  uint32_t nprobe, float radius, uint64_t reserve, vdb_range_result** out);
+/* Diagnostics: the calling thread's latest vdb_ivf_range_search_screened by step (HIP events
+ * summed over the call's batches): the pairs kernel, the bound kernel, the re-check (re-runs
+ * included); the (query, row) pairs the bound kernel judged (with a filter: of allowed rows) and
+ * those it kept; the batches served through the screen and by the exact scan. Any pointer may be
+ * NULL; a thread without a call reads zeros. */
+int vdb_range_screen_last_timing(double* pairs_ms, double* bound_ms, double* recheck_ms, uint64_t* pairs_bounded,
+                                 uint64_t* candidates, uint32_t* screened_batches, uint32_t* exact_batches);
 /* Diagnostics: the calling thread's latest vdb_ivf_filter_create(_device) (HIP events): the
  * device sort of the ids, and the mark and count kernels. Either pointer may be NULL. */
 int vdb_filter_create_last_timing(double* sort_ms, double* mark_ms);

@@ -17,6 +17,14 @@ and the copy of the result included):
           rows the masked scan reads: per list cdiv(pairs, group) reads of, in the interleaved
           layout, every 64-slot block with an allowed row, and in the row-major layout of the
           allowed rows alone (the masks recomputed on the host from the lists' ids)
+  screened  vdb_ivf_range_search_screened at the four radii, once per shadow format (screen_i8 1:
+          int8, 0: bf16; setting it rebuilds the shadow), against the exact range call on
+          the same handle in the same run: the two calls alternate, and before any timing their
+          lims, ids and distance bits are compared at the timed size. Per call the wall time, the
+          scan stage (grouping, pairs, bound and re-check against the exact scan) and its
+          pairs / bound / re-check split, the order stage, candidates and hits, and the bound
+          kernel's read rate over its own bytes: per list cdiv(pairs, 16) reads of its blocks,
+          64 x (dp or 2 dp shadow + 16 meta + 4 scale, int8 only) bytes each
 The range calls run in both list layouts a handle can hold: the interleaved arena (screen = 0)
 and the screen's row-major copy (screen = 1, after a plain search). Each figure is the median of
 `--repeats` calls after one warm-up call, with min and max. Prints one JSON line per leg.
@@ -36,6 +44,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG_DIR = os.path.join(ROOT, "cuda-acceleratedvectordatabaseengine_amd")
 GROUP = 8  # kRangeGroup: queries of a list that share one read of it
+SCREEN_GROUP = 16  # kRangeScreenGroup: pairs of a list that share one read of its shadow
 
 
 def load_vdb():
@@ -195,12 +204,60 @@ def main():
                       "hits": steps[-1]["hits"], "reruns": steps[-1]["reruns"],
                       "scan_TBps": round(rows_read * dp * 4 * passes / (scan * 1e-3) / 1e12, 3) if scan > 0 else None})
 
+        def spread(v):
+            return {"med": med(v), "min": round(min(v), 3), "max": round(max(v), 3)}
+
+        def screened():
+            blocks_read = int((-(-per_list // SCREEN_GROUP) * -(-sizes // 64)).sum())
+            for i8 in (1, 0):
+                idx.set_option("screen_i8", i8)
+                idx.set_option("screen", 1)
+                idx.search(q, nprobe=args.nprobe, k=K)  # (a live screen of this format)
+                fmt = idx.profile_read()["screen_shadow"]
+                if fmt != (2 if i8 else 1):
+                    sys.exit("range_bench: the handle holds shadow format %d, asked for screen_i8 %d" % (fmt, i8))
+                bound_bytes = blocks_read * 64 * ((dp if i8 else 2 * dp) + 16 + (4 if i8 else 0))
+                for name, r in radii:
+                    ex = idx.range_search(q, r, nprobe=args.nprobe)  # (also the warm-up calls)
+                    sc = idx.range_search(q, r, nprobe=args.nprobe, screen=True)
+                    for a, b, what in zip(ex, sc, ("lims", "distance bits", "ids")):
+                        if a.tobytes() != b.tobytes():
+                            sys.exit("range_bench: %s of the screened and the exact call differ at radius %s" % (what, name))
+                    te, ts, se, ss, sx = [], [], [], [], []
+                    for _ in range(args.repeats):  # the two calls alternate
+                        t0 = time.perf_counter()
+                        idx.range_search(q, r, nprobe=args.nprobe)
+                        te.append((time.perf_counter() - t0) * 1e3)
+                        se.append(idx.range_last_timing())
+                        t0 = time.perf_counter()
+                        idx.range_search(q, r, nprobe=args.nprobe, screen=True)
+                        ts.append((time.perf_counter() - t0) * 1e3)
+                        ss.append(idx.range_last_timing())
+                        sx.append(idx.range_screen_last_timing())
+                    bound = med([x["bound_ms"] for x in sx])
+                    emit({"what": "range_screened", "shadow": "int8" if i8 else "bf16", "radius": name, "r": r,
+                          "exact_wall_ms": spread(te), "screened_wall_ms": spread(ts),
+                          "exact_scan_ms": spread([x["scan_ms"] for x in se]),
+                          "screened_scan_ms": spread([x["scan_ms"] for x in ss]),
+                          "pairs_ms": spread([x["pairs_ms"] for x in sx]), "bound_ms": spread([x["bound_ms"] for x in sx]),
+                          "recheck_ms": spread([x["recheck_ms"] for x in sx]),
+                          "exact_order_ms": med([x["order_ms"] for x in se]),
+                          "screened_order_ms": med([x["order_ms"] for x in ss]),
+                          "pairs_bounded": sx[-1]["pairs_bounded"], "candidates": sx[-1]["candidates"],
+                          "hits": ss[-1]["hits"], "reruns": ss[-1]["reruns"],
+                          "screened_batches": sx[-1]["screened_batches"], "exact_batches": sx[-1]["exact_batches"],
+                          "bound_bytes": bound_bytes,
+                          "bound_TBps": round(bound_bytes / (bound * 1e-3) / 1e12, 3) if bound > 0 else None,
+                          "exact_scan_bytes": rows_read * dp * 4})
+            idx.set_option("screen_i8", 2)
+
         plain(0)
         ranged("interleaved")
         masked("interleaved")
         plain(1)
         ranged("row-major")
         masked("row-major")
+        screened()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:
