@@ -197,6 +197,7 @@ def lib() -> ctypes.CDLL:
                                                   ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_ivf_screen_snapshot": (ctypes.c_int, [vp, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64,
                                                    ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_coarse_snapshot": (ctypes.c_int, [vp, vp, u32, u32, vp, vp, vp, vp, vp]),
         "vdb_ivf_open_lists": (ctypes.c_int, [vp, ctypes.c_char_p]),
         "vdb_ivf_profile_enable": (ctypes.c_int, [vp, i32]),
         "vdb_ivf_profile_reset": (ctypes.c_int, [vp]),
@@ -885,6 +886,26 @@ class IVFFlatIndex:
             snap[name] = fetch(name, dtype).reshape((-1,) + tail)
         snap["ublist"] = snap["ublist"].reshape(snap["B"] * snap["P"], snap["ub_lists"], snap["k"])
         return snap
+
+    def coarse_snapshot(self, rows, nprobe: int = 0, assign: bool = False) -> dict:
+        """(diagnostics) the coarse step's buffers for `rows` (vdb_ivf_coarse_snapshot): "approx" and
+        "delta" f32 [n, nlist], the matrix-core distances and their error bounds; with nprobe > 0
+        "cand" u32 [n, nlist] (row i: its candidate lists in any order, then 0xFFFFFFFF) and "probes"
+        u32 [n, min(nprobe, nlist)]; with assign "assign" u32 [n]. Changes nothing."""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != self.dimension:
+            raise ValueError("rows must be [n, dim]")
+        n, nlist = r.shape[0], self.config.nlist
+        out = {"approx": np.empty((n, nlist), np.float32), "delta": np.empty((n, nlist), np.float32)}
+        if nprobe > 0:
+            out["cand"] = np.empty((n, nlist), np.uint32)
+            out["probes"] = np.empty((n, min(nprobe, nlist)), np.uint32)
+        if assign:
+            out["assign"] = np.empty(n, np.uint32)
+        ptr = {k: _ptr(v) for k, v in out.items()}
+        _check(lib().vdb_ivf_coarse_snapshot(self._h, _ptr(r), n, nprobe, ptr["approx"], ptr["delta"], ptr.get("cand"),
+                                             ptr.get("probes"), ptr.get("assign")))
+        return out
 
     def profile_enable(self, on: bool = True):
         _check(lib().vdb_ivf_profile_enable(self._h, int(on)))

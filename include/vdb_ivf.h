@@ -638,6 +638,24 @@ int vdb_ivf_collect_stamps(vdb_ivf* index, uint64_t* out, uint64_t cap, uint64_t
  * VDB_ERR_INVALID_ARGUMENT: a null or unknown name, a group handle, or a last batch that took
  * another route (the inline screen, the exact scan, the tier). */
 int vdb_ivf_screen_snapshot(vdb_ivf* index, const char* name, void* out, uint64_t cap_bytes, uint64_t* bytes);
+/* Diagnostics: the coarse step's buffers for n rows of the caller's ([n][dim], host memory),
+ * read-only: the rows staged as a batch's queries are (zero-padded, or brought to unit length on
+ * a VDB_METRIC_COSINE_DISTANCE handle), the matrix-core bounds over the handle's centroids by
+ * the kernel the engine would pick for n rows of this dimension, then the search's selection for
+ * nprobe (its top min(nprobe, nlist) lists by exact (distance, list)) and the add's assignment,
+ * on buffers of the call's own that are freed on return. The option coarse_mode is not consulted.
+ * Host outputs, any of which may be null: approx and delta f32[n][nlist], the approximate
+ * distance and its error bound, |approx - exact| <= delta wherever both are finite; cand
+ * u32[n][nlist], row i: the lists of row i whose interval can reach the top, in any order, then
+ * UINT32_MAX; probes u32[n][min(nprobe, nlist)]; assign u32[n]. nprobe 0 skips the selection:
+ * cand and probes must then be null. Synchronises the handle and changes nothing in it:
+ * vdb_ivf_gpu_bytes_allocated and the bits of a following search are as without the call.
+ * Refused before any launch: a null handle or null rows, a group handle, nprobe > 0 with cand
+ * and probes both null, nprobe 0 with either, n * nlist above 2^27 VDB_ERR_INVALID_ARGUMENT;
+ * VDB_METRIC_COSINE (no matrix-core path), a dimension whose query row does not fit the
+ * selection's LDS, min(nprobe, nlist) above 1024 VDB_ERR_UNSUPPORTED. */
+int vdb_ivf_coarse_snapshot(vdb_ivf* index, const float* rows, uint32_t n, uint32_t nprobe,
+                            float* approx, float* delta, uint32_t* cand, uint32_t* probes, uint32_t* assign);
 /* The tier's home on disk (ListPrefetcher::register_list_file / prefetch_lists,
  * engine/prefetcher.h:139-183; list files of format/storage.h): serve this handle's lists
  * from an index file written by vdb_ivf_save, without reading them into memory.
