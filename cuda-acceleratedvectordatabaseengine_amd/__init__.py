@@ -148,6 +148,7 @@ def lib() -> ctypes.CDLL:
         "vdb_filter_stale": (ctypes.c_int, [vp]),
         "vdb_filter_free": (None, [vp]),
         "vdb_ivf_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, vp]),
+        "vdb_ivf_search_prepared_multi": (ctypes.c_int, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp]),
         "vdb_ivf_range_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, ctypes.c_float, u64,
                                                          ctypes.POINTER(vp)]),
         "vdb_ivf_range_search_screened": (ctypes.c_int, [vp, vp, vp, u32, u32, ctypes.c_float, u64,
@@ -612,6 +613,30 @@ class IVFFlatIndex:
         D = np.empty((n, k), dtype=np.float32)
         I = np.empty((n, k), dtype=np.uint64)
         _check(lib().vdb_ivf_search_prepared(self._h, flt._f, _ptr(q), n, nprobe, k, _ptr(D), _ptr(I)))
+        return D, I
+
+    def search_prepared_multi(self, queries: np.ndarray, filters, filter_of,
+                              params: "IVFFlatIndex.SearchParams | None" = None, *, nprobe: int | None = None,
+                              k: int | None = None):
+        """One search for a batch whose queries each name their own prepared filter
+        (vdb_ivf_search_prepared_multi): query i is searched under filters[filter_of[i]]. For
+        every filter, the rows of its queries are what search_prepared returns for those queries
+        in call order. filters: a sequence of Filter. Returns (distances, indices)."""
+        p = params or IVFFlatIndex.SearchParams()
+        nprobe = p.nprobe if nprobe is None else nprobe
+        k = p.k if k is None else k
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
+        n = q.shape[0]
+        fo = np.ascontiguousarray(filter_of, dtype=np.uint32).reshape(-1)
+        if fo.shape[0] != n:
+            raise ValueError("filter_of needs one entry per query")
+        filters = list(filters)
+        # (a Filter holds a c_void_p, or None once closed: a null entry, which the library refuses)
+        tab = (ctypes.c_void_p * max(len(filters), 1))(*[getattr(f._f, "value", f._f) for f in filters])
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.uint64)
+        _check(lib().vdb_ivf_search_prepared_multi(self._h, tab, len(filters), _ptr(fo), _ptr(q), n, nprobe, k,
+                                                   _ptr(D), _ptr(I)))
         return D, I
 
     def range_search_prepared(self, queries: np.ndarray, flt: "Filter | None", radius: float, *, nprobe: int = 10,

@@ -7,6 +7,7 @@
 #include "fetch.hpp"
 #include "filter.hpp"
 #include "filter_epoch.hpp"
+#include "multi_filter.hpp"
 #include "prepared.hpp"
 #include "range.hpp"
 #include "remove.hpp"
@@ -647,6 +648,23 @@ int vdb_ivf_search_prepared(vdb_ivf* h, const vdb_filter* f, const float* q, uin
         std::lock_guard<std::mutex> g(h->mu);
         if (!h->is_group()) h->set_device();
         search_prepared(*h, *f, q, n, nprobe, k, dist, ids);
+    });
+}
+
+int vdb_ivf_search_prepared_multi(vdb_ivf* h, const vdb_filter* const* filters, uint32_t n_filters,
+                                  const uint32_t* filter_of, const float* q, uint32_t n, uint32_t nprobe, uint32_t k,
+                                  float* dist, uint64_t* ids) {
+    return guarded([&] {
+        require(h != nullptr, "null handle");  // (all of this before any device call)
+        if (n == 0) return;
+        require((q && dist && ids) || k == 0, "null argument");
+        require(filters && filter_of, "null filters or filter_of");
+        require(n_filters > 0, "no filters (n_filters == 0)");
+        for (uint32_t f = 0; f < n_filters; ++f) require(filters[f] != nullptr, "a null entry in filters");
+        for (uint32_t i = 0; i < n; ++i) require(filter_of[i] < n_filters, "filter_of names no entry of filters (out of range)");
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        search_prepared_multi(*h, filters, n_filters, filter_of, q, n, nprobe, k, dist, ids);
     });
 }
 

@@ -134,6 +134,17 @@ void IVFFlatIndex::search_prepared(const float* queries, uint32_t n_queries, con
        "search_prepared");
 }
 
+void IVFFlatIndex::search_prepared_multi(const float* queries, uint32_t n_queries, const SearchParams& params,
+                                         const Filter* const* filters, uint32_t n_filters, const uint32_t* filter_of,
+                                         float* distances, uint64_t* indices) {
+    if (!filters && n_filters) throw std::invalid_argument("search_prepared_multi: null filters");
+    std::vector<const vdb_filter*> tab(n_filters);
+    for (uint32_t f = 0; f < n_filters; ++f) tab[f] = filters[f] ? filters[f]->handle() : nullptr;
+    ok(vdb_ivf_search_prepared_multi(h_, tab.data(), n_filters, filter_of, queries, n_queries, params.nprobe, params.k,
+                                     distances, indices),
+       "search_prepared_multi");
+}
+
 void IVFFlatIndex::range_search_prepared(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
                                          const Filter& filter, std::vector<uint64_t>& lims,
                                          std::vector<float>& distances, std::vector<uint64_t>& indices) {

@@ -1,7 +1,8 @@
 // scan_items.hip — the pair grouping in front of ivf_filter_scan and ivf_range_scan (gfx950):
 // the batch's (query, probe) pairs by probed list (count, prefix, fill) and the lists' first
 // scan items (scan_items.hpp). gate[l] != 0 admits list l: the filter passes its allowed rows,
-// the range search the lists' counts.
+// the range search the lists' counts. launch_scan_group_pairs gates per pair instead (gate[i]):
+// vdb_ivf_search_prepared_multi passes the rows the pair's own filter allows in its list.
 #include "scan_kernels.hpp"
 
 namespace vdbk {
@@ -72,7 +73,35 @@ __global__ void scan_pair_fill(const uint32_t* __restrict__ probes, uint32_t BP,
     if (gate[l]) inv[pair_start[l] + atomicAdd(&cursor[l], 1u)] = i;
 }
 
+// The same two passes gated per pair (gate[i], i the pair): a list's pairs are the admitted
+// ones among those that probe it.
+__global__ void scan_pair_count_by_pair(const uint32_t* __restrict__ probes, uint32_t BP,
+                                        const uint32_t* __restrict__ gate, uint32_t* __restrict__ cursor) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= BP) return;
+    if (gate[i]) atomicAdd(&cursor[probes[i]], 1u);
+}
+
+__global__ void scan_pair_fill_by_pair(const uint32_t* __restrict__ probes, uint32_t BP,
+                                       const uint32_t* __restrict__ gate, const uint32_t* __restrict__ pair_start,
+                                       uint32_t* __restrict__ cursor, uint32_t* __restrict__ inv) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= BP) return;
+    const uint32_t l = probes[i];
+    if (gate[i]) inv[pair_start[l] + atomicAdd(&cursor[l], 1u)] = i;
+}
+
 }  // namespace
+
+void launch_scan_group_pairs(const uint32_t* probes, uint32_t BP, const uint32_t* gate, const uint32_t* count,
+                             uint32_t nlist, uint32_t segs, uint32_t group, uint32_t* cursor, uint32_t* pair_start,
+                             uint32_t* item_start, uint32_t* inv, hipStream_t s) {
+    if (!BP || !nlist) return;
+    (void)hipMemsetAsync(cursor, 0, (size_t)nlist * 4, s);
+    scan_pair_count_by_pair<<<(BP + 255) / 256, 256, 0, s>>>(probes, BP, gate, cursor);
+    scan_pair_prefix<<<1, 256, 0, s>>>(cursor, count, nlist, segs, group, pair_start, item_start);
+    scan_pair_fill_by_pair<<<(BP + 255) / 256, 256, 0, s>>>(probes, BP, gate, pair_start, cursor, inv);
+}
 
 void launch_scan_group(const uint32_t* probes, uint32_t BP, const uint32_t* gate, const uint32_t* count,
                        uint32_t nlist, uint32_t segs, uint32_t group, uint32_t* cursor, uint32_t* pair_start,

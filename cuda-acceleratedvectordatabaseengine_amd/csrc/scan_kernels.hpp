@@ -17,6 +17,13 @@ void launch_scan_group(const uint32_t* probes, uint32_t BP, const uint32_t* gate
                        uint32_t nlist, uint32_t segs, uint32_t group, uint32_t* cursor, uint32_t* pair_start,
                        uint32_t* item_start, uint32_t* inv, hipStream_t s);
 
+// The same grouping gated per pair: pair i is left out where gate[i] == 0 (gate has BP entries;
+// vdb_ivf_search_prepared_multi passes the rows the pair's own filter allows in its list). The
+// outputs mean what they mean above, so decode_scan_item serves both.
+void launch_scan_group_pairs(const uint32_t* probes, uint32_t BP, const uint32_t* gate, const uint32_t* count,
+                             uint32_t nlist, uint32_t segs, uint32_t group, uint32_t* cursor, uint32_t* pair_start,
+                             uint32_t* item_start, uint32_t* inv, hipStream_t s);
+
 // What a scan kernel reads to find its items, their rows and their queries.
 struct ScanListArgs {
     const float4* lists = nullptr;  // rows == 0: [block][d4][64] float4; rows != 0: [slot][d4] float4

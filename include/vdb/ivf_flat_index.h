@@ -106,6 +106,13 @@ public:
     // search_filtered's result for the filter's id set, without taking the masks again.
     void search_prepared(const float* queries, uint32_t n_queries, const SearchParams& params, const Filter& filter,
                          float* distances, uint64_t* indices);
+    // One search for a batch whose queries each name their own filter (a mixed-tenant batch,
+    // vdb_ivf_search_prepared_multi): query i is searched under *filters[filter_of[i]]. For every
+    // filter, the rows of its queries are what search_prepared returns for those queries in
+    // call order.
+    void search_prepared_multi(const float* queries, uint32_t n_queries, const SearchParams& params,
+                               const Filter* const* filters, uint32_t n_filters, const uint32_t* filter_of,
+                               float* distances, uint64_t* indices);
     // range_search on an index holding only the rows the filter allows.
     void range_search_prepared(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
                                const Filter& filter, std::vector<uint64_t>& lims, std::vector<float>& distances,

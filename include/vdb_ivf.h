@@ -278,7 +278,8 @@ int vdb_upsert_last_timing(double* resolve_ms, double* mark_ms, double* plan_ms,
  * handle (vdb_ivf_open_lists), a sharded handle (world > 1) and a group handle give
  * VDB_ERR_UNSUPPORTED. A filter many calls share is prepared once with vdb_ivf_filter_create
  * (below), which also takes the ids from the device. Not offered yet: the gRPC service,
- * coalescing of concurrent filtered calls. */
+ * coalescing of concurrent filtered calls (queries under different prepared filters share one
+ * call through vdb_ivf_search_prepared_multi, below). */
 enum { VDB_FILTER_EXCLUDE = 0, VDB_FILTER_INCLUDE = 1 };
 int vdb_ivf_search_filtered(vdb_ivf* index, const float* queries, uint32_t n, uint32_t nprobe, uint32_t k,
                             const uint64_t* filter_ids, uint64_t n_filter, int mode,
@@ -365,7 +366,9 @@ int vdb_range_last_timing(double* scan_ms, double* order_ms, uint64_t* pairs_sca
  * the lists are held row-major only the allowed rows' bytes are read.
  * A filter of another handle gives VDB_ERR_INVALID_ARGUMENT; what the one-shot calls refuse is
  * refused the same way; a refusal leaves the handle untouched. Every call here holds the
- * handle's lock and has finished its device work when it returns. */
+ * handle's lock and has finished its device work when it returns. Not offered yet: coalescing
+ * of concurrent prepared calls; a caller that holds queries of several filters puts them into
+ * one vdb_ivf_search_prepared_multi (below). */
 typedef struct vdb_filter vdb_filter;
 enum { VDB_FILTER_AND = 0, VDB_FILTER_OR = 1, VDB_FILTER_ANDNOT = 2 };
 int vdb_ivf_filter_create(vdb_ivf* index, const uint64_t* filter_ids, uint64_t n_filter, int mode, vdb_filter** out);
@@ -379,6 +382,44 @@ int vdb_ivf_search_prepared(vdb_ivf* index, const vdb_filter* filter, const floa
                             uint32_t nprobe, uint32_t k, float* distances, uint64_t* ids);
 int vdb_ivf_range_search_prepared(vdb_ivf* index, const vdb_filter* filter, const float* queries, uint32_t n,
                                   uint32_t nprobe, float radius, uint64_t reserve, vdb_range_result** out);
+/* Per-query prepared filters: one search for a batch whose queries each belong to their own
+ * filter (a mixed-tenant batch). filters[0..n_filters) are prepared filters of this handle and
+ * filter_of[i] < n_filters names the filter of query i; host buffers throughout, as for
+ * vdb_ivf_search_prepared. Two entries of filters[] may be the same filter; a filter no query
+ * names is still validated.
+ * For every filter index f, let S_f be the queries i with filter_of[i] == f, in call order. The
+ * result rows of S_f are, bit for bit (ids and distance bits), what vdb_ivf_search_prepared(index,
+ * filters[f], the queries of S_f, |S_f|, nprobe, k) returns: the mixed call equals the
+ * per-filter calls scattered back into request order. So the stale-slot reuse (stale_slots = 1)
+ * never crosses filters: a slot whose list has no row the query's filter allows keeps the
+ * content of the latest earlier query of the same filter whose probe at that slot had an
+ * allowed row. With stale_slots = 0, row i is the single-query prepared search of query i.
+ * Results never depend on the `batch` option. Cosine is served (every distance 0.0f, ties by
+ * id); VDB_METRIC_COSINE_DISTANCE is mapped after the last merge, as the prepared call maps it.
+ * One pass serves the batch: one upload, one coarse step, one pair grouping, and a masked exact
+ * scan that looks the mask up per query, so queries of different filters that probe the same
+ * list share the read of its blocks. A block is read where the mask of any of the (up to four)
+ * queries that share the read has a bit; a row is offered to a query only where that query's
+ * own mask has its bit.
+ * The call builds, refreshes and releases nothing: vdb_ivf_gpu_bytes_allocated is the same
+ * before and after, every filter stays live, and a following vdb_ivf_search returns the bits it
+ * returns without the call. It holds the handle's lock and has finished its device work when it
+ * returns. vdb_filter_last_timing reports it: mark_ms = 0, scan_ms and merge_ms summed over the
+ * batches, pairs_scanned the sum over the (query, probe) pairs of the rows that query's filter
+ * allows in that list.
+ * Refusals (the handle untouched, the outputs not written): VDB_ERR_INVALID_ARGUMENT, before any
+ * device call, for a null handle, for null queries, distances or ids with n > 0, for null filters
+ * or filter_of with n > 0, for n_filters == 0 with n > 0, for a null entry of filters[] and for
+ * a filter_of[i] >= n_filters; VDB_ERR_INVALID_ARGUMENT for a filter of another handle;
+ * VDB_ERR_STATE for a stale filter; VDB_ERR_UNSUPPORTED for k > 64 and for the list-cache tier,
+ * a file-home, a sharded and a group handle, exactly what vdb_ivf_search_prepared refuses. n == 0
+ * or k == 0 succeeds and touches nothing; an empty index or nprobe == 0 fills every slot with
+ * (FLT_MAX, UINT64_MAX).
+ * Not offered: the gRPC service, a device-pointer variant, per-query filters for the range
+ * search and for the screen. */
+int vdb_ivf_search_prepared_multi(vdb_ivf* index, const vdb_filter* const* filters, uint32_t n_filters,
+                                  const uint32_t* filter_of, const float* queries, uint32_t n,
+                                  uint32_t nprobe, uint32_t k, float* distances, uint64_t* ids);
 /* Range search through the screen: vdb_ivf_range_search (filter == NULL) or
  * vdb_ivf_range_search_prepared served from the shadow the screened search keeps. The result is,
  * bit for bit (lims, ids, distance bits), what the exact call returns, with its reserve, its
