@@ -6,6 +6,11 @@
 // IORING_OP_READ submissions carrying a caller tag; completions are reaped in any order.
 // When io_uring_setup is not permitted (a seccomp profile, an old kernel), the same
 // interface falls back to synchronous pread, so callers never branch on it.
+//
+// No read targets the caller's buffer: that may be page-locked memory of the HIP runtime,
+// a mapping of the GPU driver's that the kernel can refuse as a read's destination (EFAULT,
+// buffered or O_DIRECT). Every read lands in ordinary memory of the reader's own, one
+// buffer per read in flight, and is copied to the caller's buffer when it is reaped.
 #pragma once
 
 #include <linux/io_uring.h>
@@ -13,15 +18,39 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cerrno>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <memory>
+#include <new>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace vdbe {
+
+// Growable 4 KiB-aligned (O_DIRECT) ordinary host memory.
+struct ReadBuf {
+    char* p = nullptr;
+    size_t cap = 0;
+    ReadBuf() = default;
+    ReadBuf(const ReadBuf&) = delete;
+    ReadBuf& operator=(const ReadBuf&) = delete;
+    ~ReadBuf() { std::free(p); }
+    char* ensure(size_t n) {
+        if (n <= cap && p) return p;
+        std::free(p);
+        p = nullptr;
+        cap = 0;
+        if (posix_memalign((void**)&p, 4096, std::max<size_t>(n, 1)) != 0) throw std::bad_alloc();
+        cap = n;
+        return p;
+    }
+};
 
 class UringReader {
 public:
@@ -57,6 +86,8 @@ public:
         cq_mask_ = *(unsigned*)(cq + p.cq_off.ring_mask);
         cqes_ = (io_uring_cqe*)(cq + p.cq_off.cqes);
         entries_ = p.sq_entries;
+        slots_.reset(new Slot[entries_]);
+        free_all_slots();
     }
     ~UringReader() { release(); }
     UringReader(const UringReader&) = delete;
@@ -70,7 +101,7 @@ public:
     void read(int file, void* buf, uint32_t len, uint64_t off, uint64_t tag) {
         if (!uring()) {  // synchronous fallback: complete now, report at the next wait()
             int64_t got = 0;
-            char* p = (char*)buf;
+            char* p = sync_.ensure(len);
             while (got < (int64_t)len) {
                 const ssize_t r = ::pread(file, p + got, len - got, (off_t)(off + got));
                 if (r < 0 && errno == EINTR) continue;
@@ -80,20 +111,27 @@ public:
                 }
                 got += r;
             }
+            if (got > 0) std::memcpy(buf, p, (size_t)got);
             ready_.push_back({tag, got});
             return;
         }
         if (inflight_ + pending_ >= entries_) throw std::runtime_error("io_uring submission queue full");
+        const unsigned slot = free_.back();  // (one per entry: a free one exists)
+        Slot& sl = slots_[slot];
+        sl.mem.ensure(len);
+        free_.pop_back();
+        sl.dst = buf;
+        sl.tag = tag;
         const unsigned tail = *sq_tail_;
         const unsigned idx = tail & sq_mask_;
         io_uring_sqe* e = &sqes_[idx];
         std::memset(e, 0, sizeof(*e));
         e->opcode = IORING_OP_READ;
         e->fd = file;
-        e->addr = (uint64_t)(uintptr_t)buf;
+        e->addr = (uint64_t)(uintptr_t)sl.mem.p;
         e->len = len;
         e->off = off;
-        e->user_data = tag;
+        e->user_data = slot;
         sq_array_[idx] = idx;
         std::atomic_thread_fence(std::memory_order_release);
         *sq_tail_ = tail + 1;
@@ -130,7 +168,10 @@ public:
         std::atomic_thread_fence(std::memory_order_acquire);
         while (head != *cq_tail_) {
             const io_uring_cqe& c = cqes_[head & cq_mask_];
-            out.push_back({c.user_data, (int64_t)c.res});
+            const Slot& sl = slots_[c.user_data];
+            if (c.res > 0) std::memcpy(sl.dst, sl.mem.p, (size_t)c.res);
+            free_.push_back((unsigned)c.user_data);
+            out.push_back({sl.tag, (int64_t)c.res});
             ++head;
             --inflight_;
         }
@@ -146,11 +187,16 @@ public:
             while (pending_ || inflight_) (void)wait(inflight_ ? 1 : 0);
         } catch (...) {
             pending_ = inflight_ = 0;  // the ring is unusable; the owner discards the reader
+            free_all_slots();
         }
         ready_.clear();
     }
 
 private:
+    void free_all_slots() {
+        free_.clear();
+        for (unsigned i = 0; i < entries_; ++i) free_.push_back(entries_ - 1 - i);
+    }
     void release() {
         if (sqes_ && sqes_ != MAP_FAILED) ::munmap(sqes_, sqes_bytes_);
         if (cq_ptr_ && cq_ptr_ != MAP_FAILED) ::munmap(cq_ptr_, cq_bytes_);
@@ -171,6 +217,14 @@ private:
     unsigned sq_mask_ = 0, cq_mask_ = 0, entries_ = 0;
     io_uring_cqe* cqes_ = nullptr;
     unsigned inflight_ = 0, pending_ = 0;
+    struct Slot {  // one read queued or in flight
+        ReadBuf mem;  // what it lands in
+        void* dst = nullptr;
+        uint64_t tag = 0;
+    };
+    std::unique_ptr<Slot[]> slots_;  // one per ring entry; a read's user_data is its slot
+    std::vector<unsigned> free_;
+    ReadBuf sync_;  // the synchronous fallback's
     std::deque<Done> ready_;
 };
 
