@@ -148,6 +148,9 @@ def lib() -> ctypes.CDLL:
         "vdb_filter_stale": (ctypes.c_int, [vp]),
         "vdb_filter_free": (None, [vp]),
         "vdb_ivf_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, u32, vp, vp]),
+        "vdb_ivf_search_prepared_screened": (ctypes.c_int, [vp, vp, vp, u32, u32, u32, u64, vp, vp]),
+        "vdb_filter_screen_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4 +
+                                          [ctypes.POINTER(ctypes.c_uint64)] * 2 + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "vdb_ivf_search_prepared_multi": (ctypes.c_int, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp]),
         "vdb_ivf_range_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, ctypes.c_float, u64,
                                                          ctypes.POINTER(vp)]),
@@ -602,9 +605,12 @@ class IVFFlatIndex:
         return {"sort_ms": a.value, "mark_ms": b.value}
 
     def search_prepared(self, queries: np.ndarray, flt: Filter, params: "IVFFlatIndex.SearchParams | None" = None, *,
-                        nprobe: int | None = None, k: int | None = None):
+                        nprobe: int | None = None, k: int | None = None, screen: bool = False, reserve: int = 0):
         """search_filtered's result for the filter's rows, without taking the masks again
-        (vdb_ivf_search_prepared). Returns (distances, indices)."""
+        (vdb_ivf_search_prepared). Returns (distances, indices). screen=True serves the same
+        result, bit for bit, through the screen the index holds at that moment
+        (vdb_ivf_search_prepared_screened; reserve: entries of a batch's candidate buffer, 0: the
+        library's choice)."""
         p = params or IVFFlatIndex.SearchParams()
         nprobe = p.nprobe if nprobe is None else nprobe
         k = p.k if k is None else k
@@ -612,8 +618,23 @@ class IVFFlatIndex:
         n = q.shape[0]
         D = np.empty((n, k), dtype=np.float32)
         I = np.empty((n, k), dtype=np.uint64)
-        _check(lib().vdb_ivf_search_prepared(self._h, flt._f, _ptr(q), n, nprobe, k, _ptr(D), _ptr(I)))
+        if screen:
+            _check(lib().vdb_ivf_search_prepared_screened(self._h, flt._f, _ptr(q), n, nprobe, k, reserve, _ptr(D),
+                                                          _ptr(I)))
+        else:
+            _check(lib().vdb_ivf_search_prepared(self._h, flt._f, _ptr(q), n, nprobe, k, _ptr(D), _ptr(I)))
         return D, I
+
+    def filter_screen_last_timing(self) -> dict:
+        """The calling thread's latest search_prepared(..., screen=True) by step (vdb_filter_screen_last_timing)."""
+        a, b, c, d = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        p, m = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        sb, eb = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib().vdb_filter_screen_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d),
+                                                   ctypes.byref(p), ctypes.byref(m), ctypes.byref(sb), ctypes.byref(eb)))
+        return {"pairs_ms": a.value, "thresh_ms": b.value, "bound_ms": c.value, "select_ms": d.value,
+                "pairs_bounded": p.value, "candidates": m.value, "screened_batches": sb.value,
+                "exact_batches": eb.value}
 
     def search_prepared_multi(self, queries: np.ndarray, filters, filter_of,
                               params: "IVFFlatIndex.SearchParams | None" = None, *, nprobe: int | None = None,

@@ -9,6 +9,7 @@
 #include "filter_epoch.hpp"
 #include "multi_filter.hpp"
 #include "prepared.hpp"
+#include "filter_screen.hpp"
 #include "range.hpp"
 #include "remove.hpp"
 #include "remove_plan.hpp"
@@ -701,6 +702,30 @@ int vdb_range_screen_last_timing(double* pairs_ms, double* bound_ms, double* rec
     if (candidates) *candidates = g_range_screen_timing.candidates;
     if (screened_batches) *screened_batches = g_range_screen_timing.screened_batches;
     if (exact_batches) *exact_batches = g_range_screen_timing.exact_batches;
+    return VDB_OK;
+}
+
+int vdb_ivf_search_prepared_screened(vdb_ivf* h, const vdb_filter* f, const float* q, uint32_t n, uint32_t nprobe,
+                                     uint32_t k, uint64_t reserve, float* dist, uint64_t* ids) {
+    return guarded([&] {
+        require(h && f && ((q && dist && ids) || n == 0 || k == 0), "null argument");  // (before any device call)
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        search_prepared_screened(*h, *f, q, n, nprobe, k, reserve, dist, ids);
+    });
+}
+
+int vdb_filter_screen_last_timing(double* pairs_ms, double* thresh_ms, double* bound_ms, double* select_ms,
+                                  uint64_t* pairs_bounded, uint64_t* candidates, uint32_t* screened_batches,
+                                  uint32_t* exact_batches) {
+    if (pairs_ms) *pairs_ms = g_filter_screen_timing.pairs_ms;
+    if (thresh_ms) *thresh_ms = g_filter_screen_timing.thresh_ms;
+    if (bound_ms) *bound_ms = g_filter_screen_timing.bound_ms;
+    if (select_ms) *select_ms = g_filter_screen_timing.select_ms;
+    if (pairs_bounded) *pairs_bounded = g_filter_screen_timing.pairs_bounded;
+    if (candidates) *candidates = g_filter_screen_timing.candidates;
+    if (screened_batches) *screened_batches = g_filter_screen_timing.screened_batches;
+    if (exact_batches) *exact_batches = g_filter_screen_timing.exact_batches;
     return VDB_OK;
 }
 

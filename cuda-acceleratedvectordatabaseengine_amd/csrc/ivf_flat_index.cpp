@@ -134,6 +134,13 @@ void IVFFlatIndex::search_prepared(const float* queries, uint32_t n_queries, con
        "search_prepared");
 }
 
+void IVFFlatIndex::search_prepared_screened(const float* queries, uint32_t n_queries, const SearchParams& params,
+                                            const Filter& filter, float* distances, uint64_t* indices, uint64_t reserve) {
+    ok(vdb_ivf_search_prepared_screened(h_, filter.handle(), queries, n_queries, params.nprobe, params.k, reserve,
+                                        distances, indices),
+       "search_prepared_screened");
+}
+
 void IVFFlatIndex::search_prepared_multi(const float* queries, uint32_t n_queries, const SearchParams& params,
                                          const Filter* const* filters, uint32_t n_filters, const uint32_t* filter_of,
                                          float* distances, uint64_t* indices) {

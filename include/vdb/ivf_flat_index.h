@@ -106,6 +106,11 @@ public:
     // search_filtered's result for the filter's id set, without taking the masks again.
     void search_prepared(const float* queries, uint32_t n_queries, const SearchParams& params, const Filter& filter,
                          float* distances, uint64_t* indices);
+    // search_prepared's result, bit for bit, served through the screen the index holds at that
+    // moment (vdb_ivf_search_prepared_screened). reserve: entries of a batch's candidate buffer
+    // (0: the library's choice).
+    void search_prepared_screened(const float* queries, uint32_t n_queries, const SearchParams& params,
+                                  const Filter& filter, float* distances, uint64_t* indices, uint64_t reserve = 0);
     // One search for a batch whose queries each name their own filter (a mixed-tenant batch,
     // vdb_ivf_search_prepared_multi): query i is searched under *filters[filter_of[i]]. For every
     // filter, the rows of its queries are what search_prepared returns for those queries in

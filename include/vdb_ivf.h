@@ -416,7 +416,7 @@ int vdb_ivf_range_search_prepared(vdb_ivf* index, const vdb_filter* filter, cons
  * or k == 0 succeeds and touches nothing; an empty index or nprobe == 0 fills every slot with
  * (FLT_MAX, UINT64_MAX).
  * Not offered: the gRPC service, a device-pointer variant, per-query filters for the range
- * search and for the screen. */
+ * search and for the screen (vdb_ivf_search_prepared_screened, below, takes one filter). */
 int vdb_ivf_search_prepared_multi(vdb_ivf* index, const vdb_filter* const* filters, uint32_t n_filters,
                                   const uint32_t* filter_of, const float* queries, uint32_t n,
                                   uint32_t nprobe, uint32_t k, float* distances, uint64_t* ids);
@@ -461,6 +461,56 @@ int vdb_ivf_range_search_screened(vdb_ivf* index, const vdb_filter* filter, cons
  * NULL; a thread without a call reads zeros. */
 int vdb_range_screen_last_timing(double* pairs_ms, double* bound_ms, double* recheck_ms, uint64_t* pairs_bounded,
                                  uint64_t* candidates, uint32_t* screened_batches, uint32_t* exact_batches);
+/* Prepared-filter search through the screen: vdb_ivf_search_prepared served from the shadow the
+ * screened search keeps. The result is, bit for bit (ids and distance bits), what
+ * vdb_ivf_search_prepared returns for the same handle, filter, queries, nprobe and k: per
+ * (query, probe) pair the top-k by (distance, id) among the allowed rows of that list, the
+ * unique-id merge over the slots, (FLT_MAX, UINT64_MAX) in unfilled slots, the stale-slot reuse
+ * with its carry across batches, the independence of `batch`, the VDB_METRIC_COSINE_DISTANCE map
+ * after the last merge, k <= 64, every distance the reference's sequential fp32 sum. Only the
+ * bytes read differ. Opt-in: vdb_ivf_search_prepared and vdb_ivf_search_filtered keep the exact
+ * route (the whole-list thresholds of vdb_ivf_search's screen say nothing about a filter's rows;
+ * this call computes thresholds of its own, per pair, over the allowed rows).
+ * Per batch the pairs are grouped sixteen to an item and the screened search's own pairs kernel
+ * prepares them. A threshold kernel streams the int8 or bf16 shadow (a quarter or half of the
+ * fp32 bytes) through the matrix cores and finds, per pair, the exact k-th smallest of the
+ * screen's upper bounds over the allowed rows of its list (+inf if fewer than k have one that is
+ * not NaN). A bound kernel streams the shadow once more and keeps the allowed rows whose lower
+ * bound is not above that threshold: at least k allowed rows are no farther than the threshold
+ * and a discarded row is strictly farther, so it is in no top-k, whatever its id. A row, query
+ * or centroid that is huge or non-finite has no finite bound and is always kept. The kept rows'
+ * sequential fp32 distances are computed from the row-major copy and each pair's k smallest
+ * selected; the merge is vdb_ivf_search_prepared's. A block of 64 slots without an allowed row
+ * is skipped unread by both shadow passes.
+ * Routing: through the screen only while the handle holds a live one right now; the call builds,
+ * refreshes and releases nothing (vdb_ivf_gpu_bytes_allocated is the same before and after, the
+ * filter stays live, a following vdb_ivf_search returns the bits it returns without the call). A
+ * handle without a live screen (before its first search, after an add, remove, upsert or new
+ * centroids until the next search, with the option screen 0, with VDB_METRIC_COSINE) is served by
+ * vdb_ivf_search_prepared's path, unchanged.
+ * reserve is the capacity, in entries of 8 bytes, of a batch's candidate buffer (sorted on the
+ * device, so twice that is allocated); 0 chooses 4 x batch queries x nprobe x k, and no value
+ * gives more than 2^28. A batch whose bound keeps more than the buffer holds is served by the
+ * masked exact scan instead; results are identical.
+ * Refusals are exactly those of vdb_ivf_search_prepared, the handle untouched and the outputs
+ * not written: a null handle, filter or buffer and a filter of another handle
+ * VDB_ERR_INVALID_ARGUMENT; a stale filter VDB_ERR_STATE; k > 64, the list-cache tier, a
+ * file-home, a sharded and a group handle VDB_ERR_UNSUPPORTED. The call holds the handle's lock
+ * and has finished its device work when it returns. vdb_filter_last_timing reports it as it
+ * reports vdb_ivf_search_prepared (mark_ms = 0; scan_ms everything before the merge).
+ * Not offered: per-query filters (vdb_ivf_search_prepared_multi) and vdb_ivf_search_filtered
+ * through the screen, the list-cache tier, group and sharded handles, a device-pointer variant,
+ * the gRPC service. */
+int vdb_ivf_search_prepared_screened(vdb_ivf* index, const vdb_filter* filter, const float* queries, uint32_t n,
+                                     uint32_t nprobe, uint32_t k, uint64_t reserve, float* distances, uint64_t* ids);
+/* Diagnostics: the calling thread's latest vdb_ivf_search_prepared_screened by step (HIP events
+ * summed over the call's batches): the pairs kernel, the threshold kernel, the bound kernel, the
+ * candidates' sort and selection (or the masked scan of a batch that fell back); the (pair,
+ * allowed row) pairs the bound kernel judged and those it kept; the batches served through the
+ * screen and by the exact scan. Any pointer may be NULL; a thread without a call reads zeros. */
+int vdb_filter_screen_last_timing(double* pairs_ms, double* thresh_ms, double* bound_ms, double* select_ms,
+                                  uint64_t* pairs_bounded, uint64_t* candidates, uint32_t* screened_batches,
+                                  uint32_t* exact_batches);
 /* Diagnostics: the calling thread's latest vdb_ivf_filter_create(_device) (HIP events): the
  * device sort of the ids, and the mark and count kernels. Either pointer may be NULL. */
 int vdb_filter_create_last_timing(double* sort_ms, double* mark_ms);
