@@ -152,6 +152,7 @@ def lib() -> ctypes.CDLL:
         "vdb_filter_screen_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4 +
                                           [ctypes.POINTER(ctypes.c_uint64)] * 2 + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "vdb_ivf_search_prepared_multi": (ctypes.c_int, [vp, vp, u32, vp, vp, u32, u32, u32, vp, vp]),
+        "vdb_ivf_search_prepared_multi_screened": (ctypes.c_int, [vp, vp, u32, vp, vp, u32, u32, u32, u64, vp, vp]),
         "vdb_ivf_range_search_prepared": (ctypes.c_int, [vp, vp, vp, u32, u32, ctypes.c_float, u64,
                                                          ctypes.POINTER(vp)]),
         "vdb_ivf_range_search_screened": (ctypes.c_int, [vp, vp, vp, u32, u32, ctypes.c_float, u64,
@@ -638,11 +639,14 @@ class IVFFlatIndex:
 
     def search_prepared_multi(self, queries: np.ndarray, filters, filter_of,
                               params: "IVFFlatIndex.SearchParams | None" = None, *, nprobe: int | None = None,
-                              k: int | None = None):
+                              k: int | None = None, screen: bool = False, reserve: int = 0):
         """One search for a batch whose queries each name their own prepared filter
         (vdb_ivf_search_prepared_multi): query i is searched under filters[filter_of[i]]. For
         every filter, the rows of its queries are what search_prepared returns for those queries
-        in call order. filters: a sequence of Filter. Returns (distances, indices)."""
+        in call order. filters: a sequence of Filter. Returns (distances, indices). screen=True
+        serves the same result, bit for bit, through the screen the index holds at that moment
+        (vdb_ivf_search_prepared_multi_screened; reserve as for search_prepared;
+        filter_screen_last_timing reports it)."""
         p = params or IVFFlatIndex.SearchParams()
         nprobe = p.nprobe if nprobe is None else nprobe
         k = p.k if k is None else k
@@ -656,8 +660,12 @@ class IVFFlatIndex:
         tab = (ctypes.c_void_p * max(len(filters), 1))(*[getattr(f._f, "value", f._f) for f in filters])
         D = np.empty((n, k), dtype=np.float32)
         I = np.empty((n, k), dtype=np.uint64)
-        _check(lib().vdb_ivf_search_prepared_multi(self._h, tab, len(filters), _ptr(fo), _ptr(q), n, nprobe, k,
-                                                   _ptr(D), _ptr(I)))
+        if screen:
+            _check(lib().vdb_ivf_search_prepared_multi_screened(self._h, tab, len(filters), _ptr(fo), _ptr(q), n, nprobe,
+                                                                k, reserve, _ptr(D), _ptr(I)))
+        else:
+            _check(lib().vdb_ivf_search_prepared_multi(self._h, tab, len(filters), _ptr(fo), _ptr(q), n, nprobe, k,
+                                                       _ptr(D), _ptr(I)))
         return D, I
 
     def range_search_prepared(self, queries: np.ndarray, flt: "Filter | None", radius: float, *, nprobe: int = 10,

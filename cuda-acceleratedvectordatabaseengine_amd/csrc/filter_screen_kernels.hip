@@ -42,6 +42,7 @@
 
 #include "scan_common.hpp"
 #include "screen_bound.hpp"
+#include "screen_klist.hpp"
 #include "wave_topk.hpp"
 
 namespace vdbk {
@@ -50,63 +51,12 @@ namespace {
 constexpr uint32_t kWaves = 4;  // wavefronts per workgroup
 constexpr int G = (int)kFilterScreenGroup;
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ---- a wave's k smallest floats: one per lane, ascending, +inf where there is none ----------
-template <int J>
-__device__ __forceinline__ void cmpx_f(float& d, bool keep_min) {
-    const float od = xor_f<J>(d);
-    const bool take = keep_min ? od < d : d < od;
-    d = take ? od : d;
-}
-__device__ __forceinline__ void sort64_f(float& d) {
-    const int lane = lane_id();
-    static_for<1, 7>([&](auto ks) {
-        constexpr int KK = 1 << decltype(ks)::value;
-        const bool asc = (lane & KK) == 0;
-        static_for<0, decltype(ks)::value>([&](auto js) {
-            constexpr int J = (KK >> 1) >> decltype(js)::value;
-            cmpx_f<J>(d, ((lane & J) == 0) == asc);
-        });
-    });
-}
-// a and b ascending: a becomes the 64 smallest of both, ascending
-__device__ __forceinline__ void merge64_f(float& a, float b) {
-    const int lane = lane_id();
-    const float r = shfl_f(b, 63 - lane);
-    a = r < a ? r : a;
-    static_for<0, 6>([&](auto js) {
-        constexpr int J = 32 >> decltype(js)::value;
-        cmpx_f<J>(a, (lane & J) == 0);
-    });
-}
-// a wave-uniform c below the list's last element
-__device__ __forceinline__ void insert_f(float& d, float c) {
-    const int lane = lane_id();
-    const int pos = __popcll(__ballot(d < c));
-    const float up = __uint_as_float(up1_u32(__float_as_uint(d), 0u));
-    d = lane > pos ? up : (lane == pos ? c : d);
-}
-
 __device__ __forceinline__ sbound::BoundSrc bound_src(const FilterScreenArgs& a) {
     return sbound::BoundSrc{a.shadow, a.meta, a.sscale, a.pst, a.qscale, a.dp};
 }
 
 __device__ __forceinline__ bool bad_shape(const FilterScreenArgs& a, bool i8) {
     return a.dp == 0 || a.dp % (i8 ? 64u : 32u) != 0 || a.k < 1 || a.k > kFilterScreenMaxK;
-}
-
-// The workgroup's next item from the device counter ctrl[word] (the same in every wave).
-__device__ __forceinline__ uint32_t next_item(unsigned long long* ctrl, int word, uint32_t* s_item) {
-    if (threadIdx.x == 0) *s_item = (uint32_t)atomicAdd(ctrl + word, 1ull);
-    __syncthreads();
-    const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)*s_item);
-    __syncthreads();  // (read by all before thread 0 writes the next)
-    return item;
 }
 
 template <int M, bool I8>
@@ -315,7 +265,8 @@ __global__ __launch_bounds__(kWaves * 64) void ivf_filter_screen_select(const Fi
     const uint32_t wave = wave_index();
     const uint32_t pair = blockIdx.x * kWaves + wave;  // (wave-uniform)
     if (pair >= a.BP) return;
-    if (a.allowed[a.probes[pair]] == 0) return;  // nothing is written for it, as the scan writes nothing
+    // nothing is written for a pair without an allowed row, as the scan writes nothing
+    if ((a.gate ? a.gate[pair] : a.allowed[a.probes[pair]]) == 0) return;
     float4(*tile)[C4 + 1] = s_x[wave];
     const int k = (int)a.k;
     const uint64_t lo = cand_lower(a.cand, a.n, (uint64_t)pair << 32);

@@ -83,6 +83,8 @@ struct FilterSelectArgs {
     float* slot_d = nullptr;  // [B * P][k]
     uint64_t* slot_i = nullptr;
     unsigned long long* ctrl = nullptr;  // [kFsCtrlWords]
+    // per-query filters: [BP], gate[pair] == 0 for "nothing to do for this pair"; null: allowed[probes[pair]] == 0
+    const uint32_t* gate = nullptr;
 };
 // True if the select kernel serves this shape (its LDS tile: whole chunks of kRangeChunk4 float4 per row).
 inline bool filter_select_serves(const FilterSelectArgs& a) {

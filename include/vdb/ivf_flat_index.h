@@ -118,6 +118,11 @@ public:
     void search_prepared_multi(const float* queries, uint32_t n_queries, const SearchParams& params,
                                const Filter* const* filters, uint32_t n_filters, const uint32_t* filter_of,
                                float* distances, uint64_t* indices);
+    // search_prepared_multi's result, bit for bit, served through the screen the index holds at
+    // that moment (vdb_ivf_search_prepared_multi_screened). reserve: as for search_prepared_screened.
+    void search_prepared_multi_screened(const float* queries, uint32_t n_queries, const SearchParams& params,
+                                        const Filter* const* filters, uint32_t n_filters, const uint32_t* filter_of,
+                                        float* distances, uint64_t* indices, uint64_t reserve = 0);
     // range_search on an index holding only the rows the filter allows.
     void range_search_prepared(const float* queries, uint32_t n_queries, uint32_t nprobe, float radius,
                                const Filter& filter, std::vector<uint64_t>& lims, std::vector<float>& distances,

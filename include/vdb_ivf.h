@@ -416,7 +416,7 @@ int vdb_ivf_range_search_prepared(vdb_ivf* index, const vdb_filter* filter, cons
  * or k == 0 succeeds and touches nothing; an empty index or nprobe == 0 fills every slot with
  * (FLT_MAX, UINT64_MAX).
  * Not offered: the gRPC service, a device-pointer variant, per-query filters for the range
- * search and for the screen (vdb_ivf_search_prepared_screened, below, takes one filter). */
+ * search. Through the screen: vdb_ivf_search_prepared_multi_screened, below. */
 int vdb_ivf_search_prepared_multi(vdb_ivf* index, const vdb_filter* const* filters, uint32_t n_filters,
                                   const uint32_t* filter_of, const float* queries, uint32_t n,
                                   uint32_t nprobe, uint32_t k, float* distances, uint64_t* ids);
@@ -498,11 +498,49 @@ int vdb_range_screen_last_timing(double* pairs_ms, double* bound_ms, double* rec
  * file-home, a sharded and a group handle VDB_ERR_UNSUPPORTED. The call holds the handle's lock
  * and has finished its device work when it returns. vdb_filter_last_timing reports it as it
  * reports vdb_ivf_search_prepared (mark_ms = 0; scan_ms everything before the merge).
- * Not offered: per-query filters (vdb_ivf_search_prepared_multi) and vdb_ivf_search_filtered
- * through the screen, the list-cache tier, group and sharded handles, a device-pointer variant,
- * the gRPC service. */
+ * Not offered: vdb_ivf_search_filtered through the screen, the list-cache tier, group and
+ * sharded handles, a device-pointer variant, the gRPC service. Per-query filters through the
+ * screen: vdb_ivf_search_prepared_multi_screened, below. */
 int vdb_ivf_search_prepared_screened(vdb_ivf* index, const vdb_filter* filter, const float* queries, uint32_t n,
                                      uint32_t nprobe, uint32_t k, uint64_t reserve, float* distances, uint64_t* ids);
+/* Per-query prepared filters through the screen: vdb_ivf_search_prepared_multi served from the
+ * shadow the screened search keeps. The result is, bit for bit (ids and distance bits), what
+ * vdb_ivf_search_prepared_multi returns for the same handle, filters, filter_of, queries, nprobe
+ * and k: for every filter the rows of its queries are vdb_ivf_search_prepared's for those queries
+ * in call order, the stale-slot reuse never crosses filters, and results never depend on `batch`.
+ * Only the bytes read differ. Opt-in: vdb_ivf_search_prepared_multi keeps the exact route.
+ * Per batch the pairs are gated by their own filter and grouped sixteen to an item, and the
+ * screened search's own pairs kernel prepares them. The threshold and the bound kernel are those
+ * of vdb_ivf_search_prepared_screened with the mask belonging to the pair: a block of 64 slots is
+ * skipped unread by both shadow passes where none of the item's (up to sixteen) masks has a bit,
+ * and a row counts for a pair's threshold, and may become that pair's candidate, only where the
+ * pair's own mask has its bit. The kept rows' sequential fp32 distances, each pair's k smallest
+ * and the merge are vdb_ivf_search_prepared_multi's.
+ * Routing, reserve and fallback are those of vdb_ivf_search_prepared_screened: through the screen
+ * only while the handle holds a live one right now, otherwise (and for an empty index)
+ * vdb_ivf_search_prepared_multi's path, unchanged; a batch whose bound keeps more than the
+ * candidate buffer holds is served by vdb_ivf_search_prepared_multi's masked scan, with identical
+ * results. The call builds, refreshes and releases nothing (vdb_ivf_gpu_bytes_allocated is the
+ * same before and after, every filter stays live, a following vdb_ivf_search returns the bits it
+ * returns without the call). It holds the handle's lock and has finished its device work when it
+ * returns.
+ * Refusals are exactly those of vdb_ivf_search_prepared_multi, in its order, the handle untouched
+ * and the outputs not written: before any device call VDB_ERR_INVALID_ARGUMENT for a null handle,
+ * for null queries, distances or ids with n > 0, for null filters or filter_of with n > 0, for
+ * n_filters == 0 with n > 0, for a null entry of filters[] and for a filter_of[i] >= n_filters;
+ * VDB_ERR_INVALID_ARGUMENT for a filter of another handle; VDB_ERR_STATE for a stale filter;
+ * VDB_ERR_UNSUPPORTED for k > 64 and for the list-cache tier, a file-home, a sharded and a group
+ * handle.
+ * vdb_filter_screen_last_timing and vdb_filter_last_timing report this call as they report
+ * vdb_ivf_search_prepared_screened; pairs_bounded is the sum, over the (query, probe) pairs, of
+ * the rows that query's filter allows in that list.
+ * Not offered: vdb_ivf_search_filtered through the screen, per-query filters for the range
+ * search, the list-cache tier, group and sharded handles, a device-pointer variant, the gRPC
+ * service. */
+int vdb_ivf_search_prepared_multi_screened(vdb_ivf* index, const vdb_filter* const* filters, uint32_t n_filters,
+                                           const uint32_t* filter_of, const float* queries, uint32_t n,
+                                           uint32_t nprobe, uint32_t k, uint64_t reserve,
+                                           float* distances, uint64_t* ids);
 /* Diagnostics: the calling thread's latest vdb_ivf_search_prepared_screened by step (HIP events
  * summed over the call's batches): the pairs kernel, the threshold kernel, the bound kernel, the
  * candidates' sort and selection (or the masked scan of a batch that fell back); the (pair,
