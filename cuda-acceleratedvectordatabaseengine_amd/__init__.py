@@ -132,6 +132,9 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_search_filtered": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, u64, ctypes.c_int, vp, vp]),
         "vdb_filter_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_search_exhaustive": (ctypes.c_int, [vp, vp, u32, u32, vp, vp]),
+        "vdb_exhaustive_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                                      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "vdb_ivf_range_search": (ctypes.c_int, [vp, vp, u32, u32, ctypes.c_float, u64, ctypes.POINTER(vp)]),
         "vdb_range_result_n": (u32, [vp]),
         "vdb_range_result_lims": (vp, [vp]),
@@ -544,6 +547,23 @@ class IVFFlatIndex:
         a, b, c, r = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
         _check(lib().vdb_filter_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
         return {"mark_ms": a.value, "scan_ms": b.value, "merge_ms": c.value, "pairs_scanned": r.value}
+
+    def search_exhaustive(self, queries: np.ndarray, k: int = 10):
+        """The exact top-k over every stored row (vdb_ivf_search_exhaustive; not in the
+        reference): each id once at its smallest (distance, id), whatever the centroids and the
+        lists are. Returns (distances, indices); unfilled slots hold (FLT_MAX, UINT64_MAX)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
+        n = q.shape[0]
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.uint64)
+        _check(lib().vdb_ivf_search_exhaustive(self._h, _ptr(q), n, k, _ptr(D), _ptr(I)))
+        return D, I
+
+    def exhaustive_last_timing(self) -> dict:
+        """The calling thread's latest search_exhaustive by step (vdb_exhaustive_last_timing)."""
+        a, b, r, p = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib().vdb_exhaustive_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(r), ctypes.byref(p)))
+        return {"scan_ms": a.value, "merge_ms": b.value, "rows_scanned": r.value, "pairs_computed": p.value}
 
     def fetch_ids(self, ids):
         """The stored rows carrying `ids` (vdb_ivf_fetch_ids; not in the reference). Returns

@@ -4,6 +4,7 @@
 
 #include <cmath>
 
+#include "exhaustive.hpp"
 #include "fetch.hpp"
 #include "filter.hpp"
 #include "filter_epoch.hpp"
@@ -522,6 +523,25 @@ int vdb_filter_last_timing(double* mark_ms, double* scan_ms, double* merge_ms, u
     if (scan_ms) *scan_ms = g_filter_timing.scan_ms;
     if (merge_ms) *merge_ms = g_filter_timing.merge_ms;
     if (pairs_scanned) *pairs_scanned = g_filter_timing.pairs_scanned;
+    return VDB_OK;
+}
+
+int vdb_ivf_search_exhaustive(vdb_ivf* h, const float* q, uint32_t n, uint32_t k, float* dist, uint64_t* ids) {
+    return guarded([&] {
+        require(h != nullptr, "null handle");  // (before any device call)
+        require(k > 0, "k is 1..1024");
+        require((q && dist && ids) || n == 0, "null argument");
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        search_exhaustive(*h, q, n, k, dist, ids);
+    });
+}
+
+int vdb_exhaustive_last_timing(double* scan_ms, double* merge_ms, uint64_t* rows_scanned, uint64_t* pairs_computed) {
+    if (scan_ms) *scan_ms = g_exhaustive_timing.scan_ms;
+    if (merge_ms) *merge_ms = g_exhaustive_timing.merge_ms;
+    if (rows_scanned) *rows_scanned = g_exhaustive_timing.rows_scanned;
+    if (pairs_computed) *pairs_computed = g_exhaustive_timing.pairs_computed;
     return VDB_OK;
 }
 

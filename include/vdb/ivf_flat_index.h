@@ -66,6 +66,11 @@ public:
     // id is not. The result is search()'s on an index holding only the allowed rows.
     void search_filtered(const float* queries, uint32_t n_queries, const SearchParams& params, const uint64_t* ids,
                          uint64_t n_ids, bool include, float* distances, uint64_t* indices);
+    // Not in the reference: the exact top-k over every stored row (vdb_ivf_search_exhaustive),
+    // each id once at its smallest (distance, id), whatever the centroids and lists are: the
+    // ground truth nprobe is tuned against. Unfilled slots hold (FLT_MAX, UINT64_MAX).
+    void search_exhaustive(const float* queries, uint32_t n_queries, uint32_t k, float* distances,
+                           uint64_t* indices);
     // Not in the reference: the stored rows carrying the listed ids (vdb_ivf_fetch_ids), row i
     // of vectors (n_ids x dimension) for ids[i], bit for bit as stored; zeros and found[i] = 0
     // where no row carries it. vectors and found may each be null. Returns the entries found.

@@ -599,6 +599,40 @@ int vdb_ivf_search_ids(vdb_ivf* index, const uint64_t* ids, uint32_t n, uint32_t
  * its two passes, the marks and then the found rows), and the entries found. Any pointer may be
  * NULL; a thread without a call reads zeros. */
 int vdb_fetch_last_timing(double* sort_ms, double* locate_ms, double* gather_ms, uint64_t* rows_found);
+/* Exhaustive search: the exact top-k over every stored row, the ground truth nprobe is tuned
+ * against, from the index as it stands. In place of the reference's bruteforce_search_kernel
+ * (racy, not ported).
+ * For each query on its own, take the entries (d, id) of every stored row of every list (pad
+ * slots never), each id once, at its smallest (d, id); order them ascending by (d, id); the
+ * result is the first k, unfilled slots (FLT_MAX, UINT64_MAX). d is the reference's sequential
+ * fp32 sum, bit for bit (no fused multiply-add): L2 squared, inner product negated,
+ * VDB_METRIC_COSINE 0.0f for every row (so the k smallest ids), VDB_METRIC_COSINE_DISTANCE with
+ * the query normalised like in every other call, ordered by -dot and reported as 1.0f + d. -0.0f
+ * and +0.0f tie by id and the returned bits are the computed ones; NaN sorts after every number.
+ * The result does not depend on `batch`, `stale_slots`, the centroids, or how the rows are spread
+ * over the lists. Where nlist <= 1024, stale_slots = 0 and no single list stores an id twice it
+ * equals vdb_ivf_search(index, queries, n, nprobe = nlist, k), bit for bit. With an id twice
+ * inside one list the two differ: there the per-list top-k is a multiset, and the copy can crowd
+ * another row of that list out; here it cannot.
+ * Nothing moves and nothing is rebuilt: no coarse step, no pair plan, no per-list slots. The
+ * stored rows are streamed once per tile of queries (32 at k <= 64, halving as k doubles, 2 at
+ * k > 512) in storage order, from whichever fp32 copy the handle holds at that moment, the
+ * interleaved arena or the screen's row-major copy. Temporaries are the call's own. The call
+ * holds the handle's lock and has finished its device work when it returns. Host buffers.
+ * Limits of this version (the handle is untouched by a refusal): a null handle, k == 0 and null
+ * buffers with n > 0 give VDB_ERR_INVALID_ARGUMENT; n == 0 succeeds and touches no buffer; an
+ * empty index returns every slot unfilled; k > 1024, a handle in the list-cache tier, a file-home
+ * handle (vdb_ivf_open_lists), a sharded handle (world > 1) and a group handle give
+ * VDB_ERR_UNSUPPORTED. Not offered yet: a pass through the screen (bounds from the shadow, exact
+ * re-checks), filters or a radius on this call, a device-pointer variant, groups, shards and the
+ * tier, the gRPC service. */
+int vdb_ivf_search_exhaustive(vdb_ivf* index, const float* queries, uint32_t n, uint32_t k,
+                              float* distances, uint64_t* ids);
+/* Diagnostics: the calling thread's latest vdb_ivf_search_exhaustive (HIP events): the scans and
+ * the merges summed over the call's query tiles, the stored rows streamed (rows x tiles) and the
+ * (query, row) distances computed (rows x n). Any pointer may be NULL; a thread without a call
+ * reads zeros. */
+int vdb_exhaustive_last_timing(double* scan_ms, double* merge_ms, uint64_t* rows_scanned, uint64_t* pairs_computed);
 /* Persist / restore centroids and lists (IVFFlatIndex::save/load, engine/ivf_flat_index.h:66-67,
  * declared but never defined in the reference; this engine's own file format). */
 int vdb_ivf_save(vdb_ivf* index, const char* path);
