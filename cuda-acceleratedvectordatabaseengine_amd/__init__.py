@@ -135,6 +135,9 @@ def lib() -> ctypes.CDLL:
         "vdb_ivf_search_exhaustive": (ctypes.c_int, [vp, vp, u32, u32, vp, vp]),
         "vdb_exhaustive_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "vdb_ivf_search_exhaustive_screened": (ctypes.c_int, [vp, vp, u32, u32, u64, vp, vp]),
+        "vdb_exhaustive_screen_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4 +
+                                              [ctypes.POINTER(ctypes.c_uint64)] * 2 + [ctypes.POINTER(ctypes.c_uint32)] * 2),
         "vdb_ivf_range_search": (ctypes.c_int, [vp, vp, u32, u32, ctypes.c_float, u64, ctypes.POINTER(vp)]),
         "vdb_range_result_n": (u32, [vp]),
         "vdb_range_result_lims": (vp, [vp]),
@@ -548,16 +551,34 @@ class IVFFlatIndex:
         _check(lib().vdb_filter_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(r)))
         return {"mark_ms": a.value, "scan_ms": b.value, "merge_ms": c.value, "pairs_scanned": r.value}
 
-    def search_exhaustive(self, queries: np.ndarray, k: int = 10):
+    def search_exhaustive(self, queries: np.ndarray, k: int = 10, *, screen: bool = False, reserve: int = 0):
         """The exact top-k over every stored row (vdb_ivf_search_exhaustive; not in the
         reference): each id once at its smallest (distance, id), whatever the centroids and the
-        lists are. Returns (distances, indices); unfilled slots hold (FLT_MAX, UINT64_MAX)."""
+        lists are. Returns (distances, indices); unfilled slots hold (FLT_MAX, UINT64_MAX).
+        screen=True: the same result, bit for bit, read through the screen's shadow while the
+        handle holds a live screen (vdb_ivf_search_exhaustive_screened); `reserve` is the
+        candidate entries per query, 0 the library's choice (exhaustive_screen_last_timing
+        reports what was served how)."""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dimension)
         n = q.shape[0]
         D = np.empty((n, k), dtype=np.float32)
         I = np.empty((n, k), dtype=np.uint64)
-        _check(lib().vdb_ivf_search_exhaustive(self._h, _ptr(q), n, k, _ptr(D), _ptr(I)))
+        if screen:
+            _check(lib().vdb_ivf_search_exhaustive_screened(self._h, _ptr(q), n, k, reserve, _ptr(D), _ptr(I)))
+        else:
+            _check(lib().vdb_ivf_search_exhaustive(self._h, _ptr(q), n, k, _ptr(D), _ptr(I)))
         return D, I
+
+    def exhaustive_screen_last_timing(self) -> dict:
+        """The calling thread's latest search_exhaustive(..., screen=True) by step
+        (vdb_exhaustive_screen_last_timing)."""
+        a, b, c, d = (ctypes.c_double(0) for _ in range(4))
+        r, m = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        s, e = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib().vdb_exhaustive_screen_last_timing(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d),
+                                                       ctypes.byref(r), ctypes.byref(m), ctypes.byref(s), ctypes.byref(e)))
+        return {"pairs_ms": a.value, "thresh_ms": b.value, "bound_ms": c.value, "select_ms": d.value,
+                "rows_bounded": r.value, "candidates": m.value, "screened_tiles": s.value, "exact_tiles": e.value}
 
     def exhaustive_last_timing(self) -> dict:
         """The calling thread's latest search_exhaustive by step (vdb_exhaustive_last_timing)."""

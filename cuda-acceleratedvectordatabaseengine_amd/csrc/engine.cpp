@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "exhaustive.hpp"
+#include "exhaustive_screen.hpp"
 #include "fetch.hpp"
 #include "filter.hpp"
 #include "filter_epoch.hpp"
@@ -542,6 +543,33 @@ int vdb_exhaustive_last_timing(double* scan_ms, double* merge_ms, uint64_t* rows
     if (merge_ms) *merge_ms = g_exhaustive_timing.merge_ms;
     if (rows_scanned) *rows_scanned = g_exhaustive_timing.rows_scanned;
     if (pairs_computed) *pairs_computed = g_exhaustive_timing.pairs_computed;
+    return VDB_OK;
+}
+
+int vdb_ivf_search_exhaustive_screened(vdb_ivf* h, const float* q, uint32_t n, uint32_t k, uint64_t reserve,
+                                       float* dist, uint64_t* ids) {
+    return guarded([&] {
+        require(h != nullptr, "null handle");  // (before any device call)
+        require(k > 0, "k is 1..1024");
+        require((q && dist && ids) || n == 0, "null argument");
+        std::lock_guard<std::mutex> g(h->mu);
+        if (!h->is_group()) h->set_device();
+        search_exhaustive_screened(*h, q, n, k, reserve, dist, ids);
+    });
+}
+
+int vdb_exhaustive_screen_last_timing(double* pairs_ms, double* thresh_ms, double* bound_ms, double* select_ms,
+                                      uint64_t* rows_bounded, uint64_t* candidates, uint32_t* screened_tiles,
+                                      uint32_t* exact_tiles) {
+    const ExhScreenTiming& t = g_exh_screen_timing;
+    if (pairs_ms) *pairs_ms = t.pairs_ms;
+    if (thresh_ms) *thresh_ms = t.thresh_ms;
+    if (bound_ms) *bound_ms = t.bound_ms;
+    if (select_ms) *select_ms = t.select_ms;
+    if (rows_bounded) *rows_bounded = t.rows_bounded;
+    if (candidates) *candidates = t.candidates;
+    if (screened_tiles) *screened_tiles = t.screened_tiles;
+    if (exact_tiles) *exact_tiles = t.exact_tiles;
     return VDB_OK;
 }
 

@@ -77,6 +77,12 @@ void IVFFlatIndex::search_exhaustive(const float* queries, uint32_t n_queries, u
     ok(vdb_ivf_search_exhaustive(h_, queries, n_queries, k, distances, indices), "search_exhaustive");
 }
 
+void IVFFlatIndex::search_exhaustive_screened(const float* queries, uint32_t n_queries, uint32_t k, float* distances,
+                                              uint64_t* indices, uint64_t reserve) {
+    ok(vdb_ivf_search_exhaustive_screened(h_, queries, n_queries, k, reserve, distances, indices),
+       "search_exhaustive_screened");
+}
+
 uint64_t IVFFlatIndex::fetch(const uint64_t* ids, uint64_t n_ids, float* vectors, uint8_t* found) {
     uint64_t n_found = 0;
     ok(vdb_ivf_fetch_ids(h_, ids, n_ids, vectors, found, &n_found), "fetch");

@@ -71,6 +71,11 @@ public:
     // ground truth nprobe is tuned against. Unfilled slots hold (FLT_MAX, UINT64_MAX).
     void search_exhaustive(const float* queries, uint32_t n_queries, uint32_t k, float* distances,
                            uint64_t* indices);
+    // search_exhaustive's result, bit for bit, read through the screen's shadow while the index
+    // holds a live screen (vdb_ivf_search_exhaustive_screened); otherwise search_exhaustive
+    // itself. reserve: candidate entries per query, 0 the library's choice.
+    void search_exhaustive_screened(const float* queries, uint32_t n_queries, uint32_t k, float* distances,
+                                    uint64_t* indices, uint64_t reserve = 0);
     // Not in the reference: the stored rows carrying the listed ids (vdb_ivf_fetch_ids), row i
     // of vectors (n_ids x dimension) for ids[i], bit for bit as stored; zeros and found[i] = 0
     // where no row carries it. vectors and found may each be null. Returns the entries found.

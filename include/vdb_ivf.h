@@ -623,11 +623,35 @@ int vdb_fetch_last_timing(double* sort_ms, double* locate_ms, double* gather_ms,
  * buffers with n > 0 give VDB_ERR_INVALID_ARGUMENT; n == 0 succeeds and touches no buffer; an
  * empty index returns every slot unfilled; k > 1024, a handle in the list-cache tier, a file-home
  * handle (vdb_ivf_open_lists), a sharded handle (world > 1) and a group handle give
- * VDB_ERR_UNSUPPORTED. Not offered yet: a pass through the screen (bounds from the shadow, exact
- * re-checks), filters or a radius on this call, a device-pointer variant, groups, shards and the
- * tier, the gRPC service. */
+ * VDB_ERR_UNSUPPORTED. A pass through the screen (bounds from the shadow, exact re-checks) is
+ * vdb_ivf_search_exhaustive_screened (below). Not offered yet: filters or a radius on this call, a
+ * device-pointer variant, groups, shards and the tier, the gRPC service. */
 int vdb_ivf_search_exhaustive(vdb_ivf* index, const float* queries, uint32_t n, uint32_t k,
                               float* distances, uint64_t* ids);
+/* vdb_ivf_search_exhaustive's result, the same ids and the same distance bits, read through the
+ * screen: while the handle holds a live screen (built by a search with the screen option, not
+ * outdated by an add / remove / upsert / new centroids), the metric is L2, inner product or
+ * cosine distance and k <= 64, the call reads the screen's int8 or bf16 shadow twice per tile of
+ * 32 queries instead of every fp32 row once. Every (query, list) is a pair of the screened
+ * search's own pairs kernel. Pass one keeps per query the k smallest upper bounds ub over distinct
+ * ids: T is the k-th. Pass two keeps the rows with not (lb > T): k distinct ids have
+ * d <= ub <= T and a discarded row has d >= lb > T, so it is not among the first k distinct ids.
+ * The kept rows' distances are then summed from the screen's fp32 row copy exactly as the exact
+ * call sums them, and the unique top-k by (d, id) is taken. `reserve`: candidate entries per
+ * query, 0 the library's choice (max(4096, 64 k)); a tile in which a query keeps more is served
+ * by the exact call, the result identical. Otherwise (no live screen, VDB_METRIC_COSINE, k > 64,
+ * an empty index) the whole call is vdb_ivf_search_exhaustive's path, unchanged. The call never
+ * builds, refreshes or releases a screen. Refusals and limits are vdb_ivf_search_exhaustive's. */
+int vdb_ivf_search_exhaustive_screened(vdb_ivf* index, const float* queries, uint32_t n, uint32_t k,
+                                       uint64_t reserve, float* distances, uint64_t* ids);
+/* Diagnostics: the calling thread's latest vdb_ivf_search_exhaustive_screened (HIP events, summed
+ * over the call's tiles): the pairs kernel, the threshold pass with its merge, the bound pass and
+ * the select; the (query, stored row) pairs the bound pass judged and those it could not discard;
+ * the tiles served through the screen and by the exact scan. Any pointer may be NULL; a thread
+ * without a call reads zeros. */
+int vdb_exhaustive_screen_last_timing(double* pairs_ms, double* thresh_ms, double* bound_ms, double* select_ms,
+                                      uint64_t* rows_bounded, uint64_t* candidates, uint32_t* screened_tiles,
+                                      uint32_t* exact_tiles);
 /* Diagnostics: the calling thread's latest vdb_ivf_search_exhaustive (HIP events): the scans and
  * the merges summed over the call's query tiles, the stored rows streamed (rows x tiles) and the
  * (query, row) distances computed (rows x n). Any pointer may be NULL; a thread without a call

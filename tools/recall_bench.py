@@ -11,6 +11,11 @@ search_exhaustive, and then runs search over a sweep of nprobe:
   compare     (--compare, nlist <= 1024) search(nprobe = nlist) with screen = 0 and stale_slots =
               0, the only ground truth there was before, beside search_exhaustive on the same
               handle in both list layouts (the interleaved arena; the screen's row-major copy)
+  screened    per shadow format of --shadows (int8, bf16): search_exhaustive(screen=True) beside
+              search_exhaustive on the same live-screen handle: both wall times, the screened
+              call's steps (pairs, threshold, bound, select; HIP events), the candidates per
+              query, the shadow bytes streamed per second (two passes per tile) and whether a tile
+              fell back to the exact scan
 Each time is the median of `--repeats` calls after one warm-up call. Prints one JSON line per leg.
 
   python tools/recall_bench.py [--nvec 10000000 --dim 768 --nlist 4096 --queries 256 --k 10 --data iid]
@@ -43,6 +48,7 @@ def main():
     ap.add_argument("--mix-spread", type=float, default=0.35)
     ap.add_argument("--mix-sigma", type=float, default=0.1)
     ap.add_argument("--compare", action="store_true")
+    ap.add_argument("--shadows", default="int8,bf16", help="shadow formats of the screened leg ('' skips it)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
 
@@ -123,6 +129,29 @@ def main():
         if idx.profile_read()["screen_shadow"]:  # the arena is dropped: the same call on the row-major copy
             same = bool(np.array_equal(exhaustive("row-major"), truth))
             emit({"what": "layouts_agree", "same_ids": same, "screen_shadow": idx.profile_read()["screen_shadow"]})
+        for fmt in [x for x in args.shadows.split(",") if x]:
+            idx.set_option("screen_i8", 1 if fmt == "int8" else 0)  # (rebuilds the screen in that format)
+            idx.search(q, nprobe=1, k=k)
+            if idx.profile_read()["screen_shadow"] != (2 if fmt == "int8" else 1):
+                emit({"what": "screened", "shadow": fmt, "skipped": "the handle holds no screen of this format"})
+                continue
+            (De, Ie), te = timed(lambda: idx.search_exhaustive(q, k))
+            (Ds, Is), ts = timed(lambda: idx.search_exhaustive(q, k, screen=True))
+            steps = []
+            for _ in range(args.repeats):
+                idx.search_exhaustive(q, k, screen=True)
+                steps.append(idx.exhaustive_screen_last_timing())
+            st = steps[-1]
+            sm = {f: statistics.median(x[f] for x in steps) for f in ("pairs_ms", "thresh_ms", "bound_ms", "select_ms")}
+            tiles = st["screened_tiles"] + st["exact_tiles"]
+            shadow_bytes = 2 * st["screened_tiles"] * n * dim * (1 if fmt == "int8" else 2)
+            emit({"what": "screened", "shadow": fmt, "exact_wall_ms": med(te), "exact_min": round(min(te), 3),
+                  "exact_max": round(max(te), 3), "wall_ms": med(ts), "min": round(min(ts), 3), "max": round(max(ts), 3),
+                  "speedup": round(statistics.median(te) / statistics.median(ts), 3),
+                  **{f: round(v, 3) for f, v in sm.items()}, "tiles": tiles, "exact_tiles": st["exact_tiles"],
+                  "rows_bounded": st["rows_bounded"], "candidates_per_query": round(st["candidates"] / args.queries, 1),
+                  "shadow_TBps": round(shadow_bytes / ((sm["thresh_ms"] + sm["bound_ms"]) * 1e-3) / 1e12, 3),
+                  "same": bool(np.array_equal(Is, Ie) and np.array_equal(Ds.view(np.uint32), De.view(np.uint32)))})
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:
